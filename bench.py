@@ -18,11 +18,14 @@ set-up) once that path's self-test has passed on every rank, otherwise they go t
 communicator, and if that cannot be created either, through gloo-staged exchanges;
 torch.distributed (gloo) is otherwise only the bootstrap and the timing barrier.
 
-Matrix and vectors are resident in HBM before the timed region. Rank 0 prints ONE JSON line; besides
-the headline it carries the other workloads north_star names (`extras`: synthetic banded CSR at
-half-bandwidth 8 / 64 / 512 at every GPU count; on one GPU also an irregular FEM-like matrix and the
-256^3 Laplacian = one GPU's share of configs[3] under CA-BiCGStab) and the roofline fraction of every
-solver variant on the headline matrix (`variant_rooflines`).
+Matrix and vectors are resident in HBM before the timed region. Rank 0 prints ONE JSON line. A plain
+run times ONE region of exactly K iterations of the headline and nothing else (`value` = `ms_per_step`);
+with --full the line also carries the other workloads north_star names (`extras`: synthetic banded CSR
+at half-bandwidth 8 / 64 / 512 at every GPU count; on one GPU also an irregular FEM-like matrix and the
+256^3 Laplacian = one GPU's share of configs[3] under CA-BiCGStab), the roofline fraction of every
+solver variant on the headline matrix (`variant_rooflines`) and the other legs below, and the headline
+is the median of three regions. --dump-outputs DIR writes x, r and the solver's scalars after the last
+timed iteration.
 """
 from __future__ import annotations
 
@@ -117,6 +120,8 @@ def _r(v, nd=6):
     return v
 
 
+# --dump-outputs: x and r (float64) of up to this many rows each, 48 MB with the sample's row indices; longer vectors are sampled
+DUMP_MAX_ROWS = 2_000_000
 COMPACT_LIMIT = 8192      # bytes; the driver's capture parsed a 16 KB line and lost a 27 KB one (round 5) -- stay well below
 ROOF_KEYS = ("kernel", "bound", "peak", "unit", "achieved", "frac", "frac_basis", "survey_8d_frac", "algorithmic_bytes_per_launch",
              "avg_launch_ms", "traffic", "frac_of_measured_copy")
@@ -268,8 +273,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--regions", type=int, default=3, help="timed regions of exactly --steps iterations each for the headline; "
-                    "`value` is their median, every region goes into the line with its three clocks (headline_regions)")
+    ap.add_argument("--regions", type=int, default=None, help="timed regions of exactly --steps iterations each for the headline "
+                    "(default 1, with --full 3); `value` is their median, every region goes into the line with its three clocks "
+                    "(headline_regions)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: STREAM probes, the other solver variants, "
+                    "the roofline and structure legs, the RCCL leg, the extra workloads, the rocprofv3 counter passes, the CPU "
+                    "baselines and the complete record (bench_full.json). Without it a run sets up, warms up, times --steps "
+                    "iterations once and prints the result line; the --no-* options below only thin out a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed iterations, write what the headline's "
+                    "solve hands its caller after the last one -- x, the recursive residual r and the solver's scalars -- as "
+                    "float64 DIR/<name>.npy (vectors longer than %d entries: a fixed, seeded sample, its row indices in "
+                    "sample_rows.npy)" % DUMP_MAX_ROWS)
     ap.add_argument("--method", default="bicgstab", choices=list(ITER_VECTOR_BYTES_PER_ROW))
     ap.add_argument("--rows", dest="n", type=int, default=0, help="rows (default: 1602111; banded: ~24 M non-zeros)")
     ap.add_argument("--scale-decades", type=float, default=2.0)
@@ -303,6 +317,11 @@ def main():
                          "the transport adds to an iteration")
     ap.add_argument("--inner", action="store_true", help=argparse.SUPPRESS)   # the run rocprofv3 wraps for roofline.traffic
     a = ap.parse_args()
+    if not a.full:
+        # a plain run measures the headline and nothing else
+        a.no_cpu_baseline = a.no_variants = a.no_extras = a.no_traffic = a.no_laplace512 = a.no_stream = a.no_rccl_leg = True
+    if a.regions is None:
+        a.regions = 3 if a.full else 1
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU, the command the driver uses)
@@ -485,7 +504,9 @@ def main():
     K, W = a.steps, a.warmup
 
     # ------------------------------------------------------------------ workloads: this rank's row slab
-    mesh_cache = os.path.join(tempfile.gettempdir(), "bicg_mesh_cache")
+    # exported: the counter passes' inner runs (TMPDIR=/tmp under rocprofv3) must find the matrix this run generated -- generating
+    # it under the profiler takes longer than a pass may
+    mesh_cache = os.environ.setdefault("BENCH_MESH_CACHE", os.path.join(tempfile.gettempdir(), "bicg_mesh_cache"))
 
     def mesh_slab(kind, lo_hi):
         """this rank's rows of the unstructured FEM matrix; rank 0 generates (or finds) the assembled matrix first, the other ranks
@@ -598,6 +619,7 @@ def main():
             ctx.sync(); torch.cuda.synchronize(); barrier()
             dt = time.perf_counter() - t0
             res = ctx.run_end()
+            self.last_res = res
             if dist is not None:
                 t = torch.tensor([dt], dtype=torch.float64)
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -622,6 +644,27 @@ def main():
             rec_rel = float(np.sqrt(s[1] / s[2])) if s[2] > 0 else float("nan")
             ok = s[3] == 0 and np.isfinite(true_rel) and np.isfinite(rec_rel) and true_rel <= 100.0 * rec_rel + 1e-12
             return bool(ok), true_rel
+
+    def dump_outputs(lg):
+        """--dump-outputs: what the last headline region left for its caller (bicg_fetch: the iterate x and the recursive residual r,
+        every rank's rows in order; bicg_run_end: iterations, (r, r), (r0, r0), breakdown iteration) as float64 .npy files"""
+        x, r = lg.ctx.fetch()
+        if dist is not None:
+            parts = [None] * world
+            dist.all_gather_object(parts, (x, r))
+            x, r = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+        if rank != 0:
+            return
+        res = lg.last_res
+        outs = {"x": x, "r": r}
+        if len(x) > DUMP_MAX_ROWS:
+            rows = np.unique(np.random.default_rng(20240601).integers(0, len(x), DUMP_MAX_ROWS))
+            outs = {"x": x[rows], "r": r[rows], "sample_rows": rows}
+        outs["scalars"] = np.array([res.iterations, res.dot_r, res.dot_zero, res.breakdown_iteration])
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, v in outs.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), np.asarray(v, dtype=np.float64))
+        note(f"outputs of the last timed iteration written to {a.dump_outputs}: {', '.join(sorted(outs))}")
 
     # ------------------------------------------------------------------ headline workload
     stage[0] = "matrix generation / upload"
@@ -664,6 +707,9 @@ def main():
         del headline_regions[:]
         dt, res = headline(leg)
         ok, true_relres = leg.check()
+    if a.dump_outputs:
+        stage[0] = "writing the outputs"
+        dump_outputs(leg)
     head_flags_all = [k for k, v in leg.ctx.flags().items() if v]
     # multi-rank persistent launches: what the exchanges made the kernels wait (device clock, one sample per exchange)
     comm_info["wait_us"] = leg.ctx.comm_wait_stats() if world > 1 else None
@@ -720,7 +766,7 @@ def main():
                         frac=bfmt / (ms_mm * 1e-3) / 1e9 / HBM_PEAK_GBS, format_bytes=bfmt, algorithmic_bytes=b8d, survey_8d_bytes=b8d,
                         survey_8d_frac=b8d / (ms_mm * 1e-3) / 1e9 / HBM_PEAK_GBS, spmv_equivalents=None)
         del X
-    spmv_alone_ms = leg.ctx.spmv_bench(200)
+    spmv_alone_ms = leg.ctx.spmv_bench(200) if a.full else None
     if spmm_leg:
         spmm_leg["spmv_equivalents"] = spmm_leg["ms"] / spmv_alone_ms
         note(f"SpMM of 16 vectors: {1e3 * spmm_leg['ms']:.1f} us ({spmm_leg['kernel']}), {spmm_leg['spmv_equivalents']:.1f} x one product")
@@ -728,14 +774,15 @@ def main():
     # (hipExtLaunchKernelGGL on the library's compute stream): kernel durations, no launch gaps. It comes after
     # the other timed legs of this matrix: event-timed launches put the queue into a profiling mode whose switch
     # back costs the next ordinary launches ~10 ms.
-    stage[0] = "roofline leg"
-    dt_ev, res_ev = leg.timed(a.method, kernel_events=True)
-    spmv_ms = res_ev.spmv_ms_total / max(res_ev.spmv_launches, 1)
     b_spmv = spmv_bytes(plan["nnz_diag"] + plan["nnz_offd"], plan["rows"], plan["halo"])
-    achieved = b_spmv / (spmv_ms * 1e-3) / 1e9 if spmv_ms > 0 else 0.0
     fmt_spmv = min(b_spmv, leg.ctx.spmv_matrix_bytes() + 16 * plan["rows"] + 16 * plan["halo"])
-    fmt_gbps = fmt_spmv / (spmv_ms * 1e-3) / 1e9 if spmv_ms > 0 else 0.0
-    leg.timed(a.method, steps=4, warm=0)       # back to ordinary launches before the next matrix is timed
+    if a.full:
+        stage[0] = "roofline leg"
+        dt_ev, res_ev = leg.timed(a.method, kernel_events=True)
+        spmv_ms = res_ev.spmv_ms_total / max(res_ev.spmv_launches, 1)
+        achieved = b_spmv / (spmv_ms * 1e-3) / 1e9 if spmv_ms > 0 else 0.0
+        fmt_gbps = fmt_spmv / (spmv_ms * 1e-3) / 1e9 if spmv_ms > 0 else 0.0
+        leg.timed(a.method, steps=4, warm=0)       # back to ordinary launches before the next matrix is timed
     leg.close()
     comm_info["transport_used"] = transport_name
 
@@ -920,7 +967,7 @@ def main():
             sk = socket.socket(); sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]; sk.close()
             cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
                    "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", str(nrows), "--method", "pipe_bicgstab",
-                   "--steps", "400", "--warmup", "40", "--transport", "host-p2p", "--no-cpu-baseline", "--no-variants", "--no-extras",
+                   "--steps", "400", "--warmup", "40", "--transport", "host-p2p", "--full", "--no-cpu-baseline", "--no-variants", "--no-extras",
                    "--no-traffic", "--no-stream", "--no-rccl-leg", "--scale-decades", str(a.scale_decades)]
             child_full = tempfile.mktemp(prefix="bicg_bench_child_", suffix=".json", dir="/tmp")
             try:
@@ -974,7 +1021,7 @@ def main():
     traffic, traffic_detail = None, None
     if rank == 0 and world == 1 and not a.no_traffic and a.workload == "transport" and not a.matrix:
         stage[0] = "rocprofv3 counter passes"
-        inner = ["--inner", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-variants", "--no-extras", "--no-traffic",
+        inner = ["--inner", "--full", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-variants", "--no-extras", "--no-traffic",
                  "--method", a.method, "--scale-decades", str(a.scale_decades)] + (["--rows", str(a.n)] if a.n else [])
         m = measure_traffic(inner, note)
         if m:
@@ -1003,7 +1050,7 @@ def main():
         t_un, t_un_detail = None, None
         if with_traffic and rank == 0 and world == 1 and not a.no_traffic:
             stage[0] = f"rocprofv3 counter passes, mesh matrix ({kind})"
-            m = measure_traffic(["--inner", "--workload", "mesh", "--numbering", kind, "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-variants",
+            m = measure_traffic(["--inner", "--full", "--workload", "mesh", "--numbering", kind, "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-variants",
                                  "--no-extras", "--no-traffic", "--no-stream", "--method", "bicgstab", "--scale-decades", str(a.scale_decades)], note)
             if m:
                 t_un = 2.0 * m["fetch_counter_bytes"] + m["write_counter_bytes"]
@@ -1096,7 +1143,8 @@ def main():
             # those that are, + row lengths + x + y; `traffic` from the counters agrees within 2 %) -- over the launch time. The CSR
             # figure of SURVEY.md 8d (12 bytes per non-zero) stays beside it: a layout that stores no column index moves fewer bytes
             # than CSR, and the CSR bytes over the launch time (`csr_equivalent_gbps`) can exceed the HBM peak.
-            "roofline": {"kernel": "k_spmv_sell (sliced-ELL SpMV with fused dot epilogue), rank 0 share", "bound": "hbm",
+            # (a plain run has no roofline leg: --full)
+            "roofline": None if not a.full else {"kernel": "k_spmv_sell (sliced-ELL SpMV with fused dot epilogue), rank 0 share", "bound": "hbm",
                          "achieved": fmt_gbps, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": fmt_gbps / HBM_PEAK_GBS,
                          "frac_basis": "format bytes: what the stored layout has to move (uniform slices read no column index); the SURVEY.md "
                                        "8d figure (12 bytes per non-zero) is survey_8d_frac, the same matrix without uniform slices is "
@@ -1125,6 +1173,7 @@ def main():
             "timed_regions_ms": regions_ms,
             "timed_region_clocks": region_clocks,
         }
+    if rank == 0 and a.full:
         # the complete record (every timed region with its clocks, plans, flags, notes): a side file and stderr. stdout gets
         # ONE compact line (< 8 KB) formed from it -- the driver's capture could not hold the 27 KB line of round 5
         full_path = os.environ.get("BENCH_FULL_JSON", os.path.join(ROOT, "bench_full.json"))
@@ -1137,6 +1186,7 @@ def main():
                 shutil.copy(full_path, os.path.join(out_dir, "bench_full.json"))
         except OSError as e:
             note(f"bench_full.json not written: {e!r}")
+    if rank == 0:
         # (not echoed to stderr: the driver keeps a bounded tail of stdout + stderr TOGETHER, a 27 KB echo would push the line out)
         print(compact(line), file=result_out, flush=True)
 

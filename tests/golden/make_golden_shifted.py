@@ -16,6 +16,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from mpi_bicgstab_amd import synth  # noqa: E402
+import golden_io  # noqa: E402
 import ref_lib as R  # noqa: E402
 
 
@@ -36,7 +37,7 @@ def main():
         pipe_same = np.array_equal(R.solve_shifted("shifted_pipe_lopbicgstab_nooverlap", M, b, sigma, seed)["x"], pipe["x"])
         b0 = R.spmv(M, np.ones(A.rows))                        # shifted_bicgstab: the seed system is A itself
         xi = R.solve_shifted("shifted_bicgstab", M, b0, sigma, 0)
-        np.savez_compressed(os.path.join(HERE, name + ".npz"), n=A.rows, ptr=A.ptr, col=A.col, val=A.val, sigma=sigma,
+        golden_io.save(os.path.join(HERE, name + ".npz"), n=A.rows, ptr=A.ptr, col=A.col, val=A.val, sigma=sigma,
                             seed=seed, b=b, k=ref["k"], x=ref["x"], r=ref["r"], variants_bit_identical=same,
                             pipe_k=pipe["k"], pipe_x=pipe["x"], pipe_r=pipe["r"], pipe_variants_bit_identical=pipe_same,
                             xi_b=b0, xi_k=xi["k"], xi_x=xi["x"], xi_r=xi["r"])

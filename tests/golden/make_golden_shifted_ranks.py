@@ -18,6 +18,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from mpi_bicgstab_amd import synth  # noqa: E402
+import golden_io  # noqa: E402
 import ref_lib as R  # noqa: E402
 
 FUNCS = [("ref_dump_shifted", "shifted_lopbicgstab"), ("ref_dump_shifted", "shifted_pipe_lopbicgstab"),
@@ -65,7 +66,7 @@ def main():
                     out[f"{fn}_P{P}_x"] = x
                     out[f"{fn}_P{P}_r"] = r
                     print(name, fn, "P =", P, "k =", k)
-            np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
+            golden_io.save(os.path.join(HERE, name + ".npz"), **out)
 
 
 if __name__ == "__main__":

@@ -17,6 +17,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from mpi_bicgstab_amd import synth  # noqa: E402
+import golden_io  # noqa: E402
 import ref_lib as R  # noqa: E402
 
 
@@ -37,7 +38,7 @@ def main():
         sw = R.solve_switching("shifted_lopbicg_switching", M, b, sigma, seed)
         no = R.solve_switching("shifted_lopbicg_switching_noovlp", M, b, sigma, seed)
         same = no["k"] == sw["k"] and np.array_equal(no["x"], sw["x"]) and np.array_equal(no["r"], sw["r"])
-        np.savez_compressed(os.path.join(HERE, name + ".npz"), n=A.rows, ptr=A.ptr, col=A.col, val=A.val, sigma=sigma, seed=seed,
+        golden_io.save(os.path.join(HERE, name + ".npz"), n=A.rows, ptr=A.ptr, col=A.col, val=A.val, sigma=sigma, seed=seed,
                             b=b, flag_k=flag["k"], flag_x=flag["x"], flag_r=flag["r"], sw_k=sw["k"], sw_x=sw["x"], sw_r=sw["r"],
                             noovlp_bit_identical=same)
         print(name, "k =", flag["k"], sw["k"], "noovlp identical:", same)

@@ -42,6 +42,8 @@ def test_bench_json_keys_are_the_contract():
     for wl in ("banded", "fem_like", "laplace7", "mesh"):
         assert f'"{wl}"' in src
     assert "--half-bandwidth" in src and "--no-extras" in src and "--no-traffic" in src
+    # a plain run times the headline only; everything else is behind --full, the outputs of the timed path behind --dump-outputs
+    assert '"--full"' in src and '"--dump-outputs"' in src and "DUMP_MAX_ROWS" in src
     for key in ("value", "unit", "cores", "kind", "sample"):
         assert re.search(rf'\b{key}=|"{key}"', open(os.path.join(ROOT, "tools", "cpu_baseline.py")).read()), key
 
@@ -49,7 +51,7 @@ def test_bench_json_keys_are_the_contract():
 def test_bench_names_the_bound_of_every_leg():
     """round 4: every variant / extra entry carries `bound` (hbm | mall | lds | latency) and `frac` against that bound only
     (bench.py roof()); the latency-bound persistent iterations claim no bandwidth fraction; the two-ranks-with-halo leg and the
-    512^3 residual check are part of the default line"""
+    512^3 residual check are part of the --full line"""
     src = open(os.path.join(ROOT, "bench.py")).read()
     for key in ('bound="latency"', 'bound="mall"', 'bound="hbm"', "mall_read8", "small_rank_with_halo", "true_relres_after_timed_region"):
         assert key in src, key

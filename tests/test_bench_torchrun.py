@@ -37,7 +37,7 @@ def _walk_roofs(d, path=""):
 def run_bench(n, extra=()):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "20", "--warmup", "5",
-           "--no-cpu-baseline", "--no-variants", *extra]
+           "--full", "--no-cpu-baseline", "--no-variants", *extra]
     return _run(cmd, 400, dict(BENCH_WATCHDOG_S="240", OMP_NUM_THREADS="2"))
 
 
@@ -114,7 +114,7 @@ def rfst(d):
 def test_bench_single_gpu_line_has_every_leg():
     """the N = 1 line the driver records: headline unchanged, plus roofline fractions of every variant, the banded /
     FEM-like / 256^3-Laplacian legs and the HBM traffic measured in this run (rocprofv3 PMC passes)"""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"]
     d = _run(cmd, 900, dict(BENCH_WATCHDOG_S="800"))
     assert d["n_gpus"] == 1 and d["config"]["iterations_genuine"] is True and "configs[1]" in d["config"]["workload"]
     for m in ("bicgstab", "ca_bicgstab", "pipe_bicgstab", "pipe_bicgstab_rr", "shifted_lopbicgstab_16shifts", "shifted_pipe_lopbicgstab_16shifts"):
@@ -204,3 +204,29 @@ def test_bench_single_gpu_line_has_every_leg():
     assert rf["traffic"] is not None, "rocprofv3 counter passes did not deliver"
     assert 0.85 * rf["format_bytes_per_launch"] < rf["traffic"] < 1.5 * rf["format_bytes_per_launch"], rf
     assert 1.7 < rf["traffic_detail"]["fetch_factor_reproducing_k_vec_FPlainQ"] < 2.3
+
+
+def test_bench_plain_run_times_the_headline_only(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one region of exactly K iterations, the contract's keys with their
+    meaning, no other leg and no complete record; --dump-outputs writes x, r and the solver's scalars of the last iteration as float64,
+    and two runs with the same arguments start from the same inputs"""
+    import numpy as np
+
+    def plain(dump):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5", "--dump-outputs", str(dump)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path), env=dict(os.environ, BENCH_WATCHDOG_S="240"))
+        assert out.returncode == 0 and out.stdout.count("\n") == 1 and out.stdout.startswith("{"), out.stdout[-2000:] + out.stderr[-4000:]
+        return json.loads(out.stdout)
+    d = plain(tmp_path / "a")
+    assert d["steps"] == 30 and d["warmup"] == 5 and d["n_gpus"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is False
+    assert d["unit"] == "ms/iteration" and d["metric"].startswith("ms/iteration, bicgstab") and d["value"] == d["ms_per_step"] > 0
+    assert d["config"]["iterations_genuine"] is True and d["full_record"] is None
+    assert d["roofline"] is None and d["cpu_baseline"] is None and not d["extras"] and not d["variants_ms_per_iteration"]
+    n = d["config"]["rows"]
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("x", "r", "scalars")}
+    assert all(v.dtype.name == "float64" for v in got.values())
+    assert got["x"].shape == got["r"].shape == (n,) and got["scalars"][0] == 35
+    assert np.isfinite(got["x"]).all() and np.isfinite(got["r"]).all() and got["scalars"][1] > 0 and got["scalars"][2] > 0
+    plain(tmp_path / "b")
+    again = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in ("x", "r", "scalars")}
+    assert again["scalars"][0] == 35 and np.allclose(again["x"], got["x"], rtol=1e-6, atol=1e-12)

@@ -505,16 +505,20 @@ def test_value_conversion_is_correctly_rounded():
 
 
 REF_DUMP = os.path.join(ROOT, "oracle", "_ref", "ref_dump")
+REF_BLOCKS = os.path.join(ROOT, "tests", "golden", "ref_loader_blocks_fem4000.json")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_DUMP), reason="oracle/_ref not built (needs /root/reference at build time)")
 @pytest.mark.parametrize("world", [1, 2, 3])
 def test_loader_against_the_reference_loader_itself(tmp_path, world):
     """The pin of SURVEY.md section 8f N1: the blocks of the C host's loader, in all its modes (serial with 1 and 4
     threads, MPI with 1 and 3 threads per rank), against the blocks the REFERENCE's own MPI_csr_load_matrix_block builds
     from the same file (oracle/_ref/ref_dump, the real src/matrix.c:268-419 compiled by oracle/Makefile) -- row pointers,
     columns in stored order, values bit for bit, partition arrays. The file is in shuffled order with 17-digit values,
-    short values, exponents and a comment block, on an irregular matrix."""
+    short values, exponents and a comment block, on an irregular matrix. The SHA-256 of the reference's rank files is
+    stored (tests/golden/ref_loader_blocks_fem4000.json): where oracle/_ref is not built, the loader is held to those."""
+    import hashlib
+    import json
+    golden = json.load(open(REF_BLOCKS))
     A = synth.fem_like(4000, seed=11, scale_decades=1.5)
     row, col, val = A.to_coo()
     rng = np.random.default_rng(8)
@@ -527,11 +531,14 @@ def test_loader_against_the_reference_loader_itself(tmp_path, world):
         f.write(f"{A.rows} {A.cols} {len(val)}\n")
         for k, (i, j, v) in enumerate(zip(row.tolist(), col.tolist(), val.tolist())):
             f.write(f"{i + 1} {j + 1} {v!r}\n" if k % 3 else f"{i + 1}  {j + 1}\t{v:.16e}\n")
-    ref = str(tmp_path / "ref")
-    done = subprocess.run([MPIEXEC, "-n", str(world), REF_DUMP, mtx, "blocks", ref], capture_output=True, text=True, timeout=300)
-    if done.returncode != 0 and "unknown method" in done.stderr:
-        pytest.skip("oracle/_ref/ref_dump predates the 'blocks' mode: rebuild with make -C oracle")
-    assert done.returncode == 0, done.stderr[-400:]
+    sha = lambda path: hashlib.sha256(open(path, "rb").read()).hexdigest()
+    assert sha(mtx) == golden["mtx_sha256"]                  # the file the stored digests were taken from
+    want_sha = golden[str(world)]
+    if os.path.exists(REF_DUMP):
+        ref = str(tmp_path / "ref")
+        done = subprocess.run([MPIEXEC, "-n", str(world), REF_DUMP, mtx, "blocks", ref], capture_output=True, text=True, timeout=300)
+        assert done.returncode == 0, done.stderr[-400:]
+        assert [sha(f"{ref}.rank{rank}.bin") for rank in range(world)] == want_sha
     for mode, threads in (("serial", "1"), ("serial", "4"), ("mpi", "1"), ("mpi", "3")):
         if mode == "mpi" and world == 1:
             continue
@@ -539,6 +546,4 @@ def test_loader_against_the_reference_loader_itself(tmp_path, world):
         subprocess.run([MPIEXEC, "-n", str(world), DUMP, mtx, out, mode], check=True, timeout=300,
                        env=dict(os.environ, BICG_MTX_THREADS=threads))
         for rank in range(world):
-            want = open(f"{ref}.rank{rank}.bin", "rb").read()
-            got = open(f"{out}.rank{rank}.bin", "rb").read()
-            assert got == want, (mode, threads, rank)
+            assert sha(f"{out}.rank{rank}.bin") == want_sha[rank], (mode, threads, rank)

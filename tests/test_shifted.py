@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import golden_io
 import oracle_lib as O
 from mpi_bicgstab_amd import synth
 
@@ -13,7 +14,7 @@ GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "shi
 
 
 def _load(path):
-    g = np.load(path)
+    g = golden_io.load(path)
     n = int(g["n"])
     A = synth.CSR(n, n, g["ptr"], g["col"], g["val"])
     return g, A

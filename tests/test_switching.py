@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import golden_io
 import oracle_lib as O
 
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "switching_*.npz")))
@@ -22,13 +23,13 @@ def _coo(g):
 
 def test_fixtures_present():
     assert len(GOLDEN) >= 4
-    assert all(bool(np.load(p)["noovlp_bit_identical"]) for p in GOLDEN)     # _noovlp is an arithmetic twin
-    assert sum(int(np.load(p)["sw_k"]) - 1 != int(np.load(p)["flag_k"]) for p in GOLDEN) >= 2   # switches change the course
+    assert all(bool(golden_io.load(p)["noovlp_bit_identical"]) for p in GOLDEN)     # _noovlp is an arithmetic twin
+    assert sum(int(golden_io.load(p)["sw_k"]) - 1 != int(golden_io.load(p)["flag_k"]) for p in GOLDEN) >= 2   # switches change the course
 
 
 @pytest.mark.parametrize("path", GOLDEN, ids=lambda p: os.path.basename(p)[:-4])
 def test_oracle_bitexact_vs_reference(path):
-    g = np.load(path)
+    g = golden_io.load(path)
     n, row, col, val = _coo(g)
     flag = O.solve_switching(n, row, col, val, g["b"], g["sigma"], int(g["seed"]), which="shifted_lopbicg")
     assert flag["k"] == int(g["flag_k"])
@@ -44,7 +45,7 @@ def test_oracle_bitexact_vs_reference(path):
 def test_oracle_switching_virtual_ranks(P):
     """the distributed restatement (P virtual ranks) follows the same course as P = 1: same number of
     switches and final seed, iteration counts within 1, solutions to 1e-9"""
-    g = np.load([p for p in GOLDEN if "lin8" in p][0])
+    g = golden_io.load([p for p in GOLDEN if "lin8" in p][0])
     n, row, col, val = _coo(g)
     one = O.solve_switching(n, row, col, val, g["b"], g["sigma"], int(g["seed"]))
     many = O.solve_switching(n, row, col, val, g["b"], g["sigma"], int(g["seed"]), nranks=P)
@@ -69,7 +70,7 @@ def test_hip_switching_vs_reference_fixture(path, which):
     scalar recurrences use the reference's operation order; only the dot products associate
     differently, so the course (iteration count, stop flags, the seed switch) is the same and the
     solutions agree to the solver tolerance."""
-    g = np.load(path)
+    g = golden_io.load(path)
     ctx, A = _ctx(g)
     key = "flag" if which == "shifted_lopbicg" else "sw"
     sigma, seed = g["sigma"], int(g["seed"])
@@ -103,7 +104,7 @@ def test_hip_switching_vs_reference_fixture(path, which):
 @pytest.mark.gpu
 def test_hip_switching_host_check_interval_does_not_matter():
     """the device pauses itself at a seed switch: iterating in chunks of 1 or 50 gives the same bits"""
-    g = np.load([p for p in GOLDEN if "transport" in p][0])
+    g = golden_io.load([p for p in GOLDEN if "transport" in p][0])
     ctx, A = _ctx(g)
     a = ctx.solve_shifted(g["b"], g["sigma"], int(g["seed"]), which="shifted_lopbicg_switching", tol=1e-12, check_every=1)
     b = ctx.solve_shifted(g["b"], g["sigma"], int(g["seed"]), which="shifted_lopbicg_switching", tol=1e-12, check_every=50)
@@ -117,7 +118,7 @@ def test_hip_switching_dropin_symbols():
     """the reference call surface of src/shifted_switching_solver.h:10-12 on host arrays"""
     import ctypes as C
     from mpi_bicgstab_amd import hipsolver as H
-    g = np.load([p for p in GOLDEN if "lin8" in p][0])
+    g = golden_io.load([p for p in GOLDEN if "lin8" in p][0])
     ctx, A = _ctx(g)
     ctx.close()
     blocks = H.single_rank_blocks(A)
@@ -155,7 +156,7 @@ def test_oracle_shifted_family_bitexact_at_P_ranks(path, P):
     """Every shifted solver of the oracle, run over P virtual ranks, reproduces the real reference at P MPI
     ranks bit for bit: shifted_lopbicgstab, shifted_pipe_lopbicgstab, shifted_bicgstab
     (src/shifted_solver.c) and shifted_lopbicg, shifted_lopbicg_switching (src/shifted_switching_solver.c)."""
-    g = np.load(path)
+    g = golden_io.load(path)
     n, row, col, val = _coo(g)
     sigma, seed = g["sigma"], int(g["seed"])
     assert len(RANKS) >= 2

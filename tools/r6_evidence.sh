@@ -56,7 +56,7 @@ for set in FETCH_SIZE WRITE_SIZE "TCP_TCC_READ_REQ_sum TCC_EA0_RDREQ_sum TCC_HIT
 done
 cd $R
 s=$(date +%s)
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_stderr.txt
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_line.json 2> $OUT/bench_stderr.txt
 echo "bench.py wall seconds: $(( $(date +%s) - s ))" >> $OUT/bench_stderr.txt
 cp bench_full.json $OUT/bench_full.json
 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|Error|error|assert" | tail -12 > $OUT/gpu_suite.txt

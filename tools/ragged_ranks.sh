@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 for numbering in rcm generator; do
   for fused in 1 0; do
     for method in bicgstab pipe_bicgstab; do
-      BICG_PLAN="halo-fused=$fused" python $R/bench.py --gpus 2 --workload mesh --numbering $numbering --method $method --transport host-p2p \
+      BICG_PLAN="halo-fused=$fused" python $R/bench.py --gpus 2 --full --workload mesh --numbering $numbering --method $method --transport host-p2p \
         --no-extras --no-variants --no-cpu-baseline --no-stream --no-rccl-leg --steps 100 --warmup 20 > /tmp/line.json 2> /tmp/err.txt
       python - <<PY
 import json
