@@ -440,6 +440,21 @@ int bicg_set_plan_threads(int n);
 int bicg_persist_plan(const CSR_Matrix *diag, const CSR_Matrix *offd_renumbered, unsigned int gmax, unsigned int summary[8],
                       unsigned int *pbase, unsigned short *pslot, double *pval, unsigned short *rlen, unsigned short *rdiag,
                       unsigned int *win_ptr, unsigned int *win_runs);
+/* The sliced-ELL plan of a diag block (host only, what bicg_create plans before it uploads anything), read
+ * with the switches of the environment, as numbers a test can pin. diag: this rank's diag block; offd_renumbered: its offd block
+ * (only the row pointers are read: which rows touch the halo), NULL for one rank; rows_global / nnz_diag_global: rows and diag
+ * non-zeros of ALL ranks (what bicg_create learns from its first collective).
+ * summary = {0 jagged layout, 1 16-bit column offsets, 2 fused-window clusters, 3 x windows (0 none, 1 runs, 2 list-driven),
+ *   4 group selection retried, 5 rows over lanes, 6 sliced-ELL entries, 7 their non-zeros, 8 their rows, 9 uniform entries,
+ *   10 constant entries, 11 masked rows, 12 CSR row blocks, 13 interior groups, 14 halo-touching groups, 15 CSR-order 16-bit
+ *   offsets, 16 window slots, 17 most runs of a window, 18 windows within 16 bits of their group, 19 most entries of a jagged
+ *   slice behind its rows' 16th, 20 halo-touching row blocks, 21 lane info present}.
+ * digest = 64-bit FNV-1a over the bytes of {0 slice_len, 1 slice_base, 2 slice_base16, 3 sval, 4 scol, 5 scol16, 6 perm,
+ *   7 group_is_sell, 8 gl_int, 9 gl_bnd, 10 bint, 11 bbnd, 12 win_ptr, 13 win_runs, 14 list, 15 lptr, 16 total, 17 ubase, 18 vbase,
+ *   19 mbase, 20 uoff, 21 uval, 22 rmask, 23 lane_info, 24 dcol16, 25 the FusedWindow} (an array the plan does not have: the
+ *   digest of no bytes). Returns 0 on success. */
+int bicg_sell_plan_digest(const CSR_Matrix *diag, const CSR_Matrix *offd_renumbered, int nranks, unsigned int rows_global,
+                          unsigned long long nnz_diag_global, unsigned long long summary[22], unsigned long long digest[26]);
 
 /* Matrix-Market block loader (host only): what MPI_csr_load_matrix_block produces for `rank` of
  * `nranks` (reference src/matrix.c:402-419) -- diag block with local columns, offd block with global

@@ -1,8 +1,14 @@
-// bicg_create.cpp -- building a context: the plan of the diag block (sliced-ELL layouts, lists, descriptors, the stencil and
-// persistent plans), device uploads, streams, and tearing it down again. Split from bicg_solver.cpp in round 5; see bicg_host.h.
+// bicg_create.cpp -- building a context. bicg_create reads as a table of contents: facts shared by all ranks, halo plan,
+// the plan of the diag block (made on the host by sell_plan_host, bicg_sell_plan.cpp), sell_plan_upload -- the only place that
+// turns that plan into device memory and adds up the matrix's bytes --, slice descriptors and the stencil plan, the peer-to-peer
+// transport, and the tail it shares with bicg_create_device_csr (ctx_finish: state, persistent set-up, streams, code objects);
+// tearing a context down again. Split from bicg_solver.cpp in round 5; see bicg_host.h.
 #include "bicg_host.h"
 
 std::vector<bicg_ctx *> g_live;
+
+// BICG_PLAN_TRACE (a user switch: the plan's stages and their seconds on stderr), read here only
+static const char *plan_trace_env() { return getenv("BICG_PLAN_TRACE"); }
 
 bool all_ranks(Comm *comm, bool mine)
 {
@@ -59,7 +65,6 @@ static void build_slice_desc(bicg_ctx *c, uint32_t nslices, uint32_t nrows, cons
         }
     }
     c->s_desc = dev_upload(d.data(), d.size());
-    c->matrix_bytes += 8ull * nslices;          // 16 bytes of descriptor per slice where base + length were counted
     if (all_lists) build_stencil_plan(c, nslices, nrows, d, uoff, uval, rmask_host);
 }
 
@@ -218,7 +223,7 @@ static void build_stencil_plan(bicg_ctx *c, uint32_t nslices, uint32_t nrows, co
     // what this product streams from the matrix side: 4 bytes per slice, one byte per row of the masked x segments
     // (the wide form: 4 bytes per `wide` slices)
     c->stencil_matrix_bytes = 4ull * nslices / (wide ? wide : 1u) + (uint64_t)cmask.size();
-    if (getenv("BICG_PLAN_TRACE"))
+    if (plan_trace_env())
         fprintf(stderr, "bicgstab_hip: plane-marching product: %u x %u x %u grid (x segments of 64 rows: %u), %zu list pairs, %u masked x segments, %u lines x %u planes per wavefront, %u rows per lane, %u workgroups\n",
                 sy, ny, nz, nxs, tab.size(), nmc, lines, zl, wide ? wide : 1u, stencil_grid(c->st));
 }
@@ -349,139 +354,6 @@ bool persist_build(bicg_ctx *c, const CSR_Matrix *diag, const std::vector<uint32
     return true;
 }
 
-// niter iterations of pipe_bicgstab in one launch (the open dot group has been closed: fetch_scal precedes every chunk)
-bool persist_chunk(bicg_ctx *c, int niter)
-{
-    if (c->grp.active) die("internal", "persistent chunk with an open dot group");
-    if (c->f1_done) die("internal", "persistent chunk after phase 1 of the next iteration has run");
-    const bool plain = c->method == BICG_BICGSTAB;
-    const bool pipe = c->method >= BICG_PIPE_BICGSTAB;
-    const unsigned groups = plain ? 3u : 2u;                  // dot groups (tags, mailbox numbers) per iteration
-    PersistArgs a = c->persist;
-    a.v = c->v; a.S = c->S; a.alarm = c->alarm; a.niter = niter;
-    a.seq0 = c->persist_seq;
-    a.vseq0 = c->persist_vseq;
-    // the pipelined kernel numbers hand-offs and groups densely and reports what it used (replacement iterations and drift
-    // checks make the count data dependent): persist_account() advances the counters after the launch
-    if (!pipe) c->persist_seq += groups * (unsigned)niter;
-    a.it0 = c->it;
-    a.krr = c->method == BICG_PIPE_BICGSTAB_RR ? c->opt.krr : 0; a.nrr = c->opt.nrr;
-    a.force_first = 0;
-    a.drift_every = (pipe && c->opt.rr_drift > 0.0) ? c->opt.check_every : 0;
-    a.drift_tol2 = c->opt.rr_drift * c->opt.rr_drift;
-    a.timeout_ticks = c->p2p ? c->p2p->timeout_ticks : 200000000ull;          // 2 s inside one GPU
-    static const int xcd_map = knob_x("BICG_PERSIST_XCD") ? atoi(knob_x("BICG_PERSIST_XCD")) : 1;
-    a.xcd_map = xcd_map;
-    static const int first_sleep = knob_x("BICG_PERSIST_SLEEP") ? atoi(knob_x("BICG_PERSIST_SLEEP")) : 1;
-    a.first_sleep = (unsigned)first_sleep;
-    if (a.multi) {
-        // every rank advances its exchange and group numbers by the whole chunk, converged early or not
-        a.halo_seq0 = c->halo_seq;
-        a.p2p = c->p2p->red_desc(c->p2p->red_seq);
-        if (!pipe) { c->halo_seq += 2u * (unsigned)niter; c->p2p->red_seq += groups * (unsigned)niter; }
-        a.ring = c->halo_ring;
-        c->halo_unsynced = 0;
-    }
-    if (a.multi) {
-        if (!c->waitlog) { c->waitlog = dev_alloc<unsigned>(3 * (size_t)kWaitCap); BICG_HIP(hipMemsetAsync(c->waitlog, 0, sizeof(unsigned) * 3 * kWaitCap, c->sc)); }
-        a.waitlog = c->waitlog; a.waitcap = kWaitCap;
-    }
-    static const bool want_trace = knob_x("BICG_PERSIST_TRACE") != nullptr;
-    unsigned long long *dbg = nullptr;
-    if (want_trace) {
-        dbg = dev_alloc<unsigned long long>(64 * 16);
-        BICG_HIP(hipMemset(dbg, 0, 64 * 16 * sizeof(unsigned long long)));
-        a.dbg = dbg;
-    }
-    hipError_t err;
-    if (plain) err = launch_plain_persist(a, c->sc);
-    else if (c->method == BICG_CA_BICGSTAB) err = launch_ca_persist(a, c->sc);
-    else err = launch_pipe_persist(a, c->sc);
-    if (err != hipSuccess) {
-        // nothing ran: hand the chunk back to the multi-launch kernels (every rank sees the same failure: same kernel, same
-        // plan limits; the sequence numbers reserved above are simply skipped on all of them)
-        if (dbg) (void)hipFree(dbg);
-        if (c->nranks > 1) die("persistent kernel", "launch failed on a multi-rank run (BICG_PERSIST=0 selects the multi-launch iteration)");
-        fprintf(stderr, "bicgstab_hip: falling back to the multi-launch iteration\n");
-        c->persist_on = false;
-        return false;
-    }
-    if (want_trace && c->method != BICG_PIPE_BICGSTAB) { BICG_HIP(hipStreamSynchronize(c->sc)); BICG_HIP(hipFree(dbg)); }
-    if (want_trace && c->method == BICG_PIPE_BICGSTAB) {
-        // 10 ns ticks of one row workgroup (0 start, 1 z and partials published, 2 window staged, 3 product done, 4 omega here,
-        // 5 w and partials published, 6 window, 7 product, 8 scalars here) and of the helper (10 / 11: group 1 / 2 published)
-        std::vector<unsigned long long> h(64 * 16);
-        BICG_HIP(hipStreamSynchronize(c->sc));
-        BICG_HIP(hipMemcpy(h.data(), dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        BICG_HIP(hipFree(dbg));
-        for (int it = std::max(0, std::min(niter, 32) - 5); it < std::min(niter, 32); ++it)
-            for (int who = 0; who < 2; ++who) {
-                const unsigned long long *q = h.data() + (size_t)(it * 2 + who) * 16, *q0 = h.data() + (size_t)(it * 2) * 16;
-                fprintf(stderr, "persist trace it %2d %s:", it, who ? "comm" : "row ");
-                for (int i = 0; i <= 8; ++i) fprintf(stderr, " %d:%+.2f", i, 0.01 * (double)(long long)(q[i] - q0[0]));
-                if (!who) fprintf(stderr, "  helper g1 %+.2f g2 %+.2f", 0.01 * (double)(long long)(q[10] - q0[0]), 0.01 * (double)(long long)(q[11] - q0[0]));
-                else fprintf(stderr, "  helper g1: arrived %+.2f summed %+.2f applied %+.2f", 0.01 * (double)(long long)(q[12] - q0[0]),
-                             0.01 * (double)(long long)(q[13] - q0[0]), 0.01 * (double)(long long)(q[14] - q0[0]));
-                fprintf(stderr, "\n");
-            }
-    }
-    return true;
-}
-
-// niter iterations of shifted_pipe_lopbicgstab (reference src/shifted_solver.c:794-866) in one launch: the seed system's
-// pipelined recurrence with products of A + sigma_seed I, every other shift's p_j / x_j streamed through in phase 2. Sequence
-// numbers as for the pipelined kernel (dense, reported back: persist_account).
-bool persist_chunk_shifted(bicg_ctx *c, int mode, int niter, int it0, int nsig, int seed, double shift)
-{
-    const bool pipe = mode == SH_PIPE;          // else shifted_lopbicgstab: three groups and two products per iteration, numbered
-                                                // like the plain kernel's (fixed counts, advanced here)
-    if (c->grp.active) die("internal", "persistent chunk with an open dot group");
-    const size_t st = c->stride;
-    PersistArgs a = c->persist;
-    a.v = c->v;
-    a.v.x = c->x_set + (size_t)seed * st; a.v.p = c->p_set + (size_t)seed * st;      // x[seed], p[seed]
-    a.S = c->S; a.alarm = c->alarm; a.niter = niter;
-    a.seq0 = c->persist_seq; a.vseq0 = c->persist_vseq;
-    a.it0 = it0; a.krr = 0; a.nrr = 0; a.force_first = 0; a.drift_every = 0; a.drift_tol2 = 0.0;
-    a.pset = c->p_set; a.xset = c->x_set; a.set_stride = (uint32_t)st; a.nsig = nsig; a.seed = seed;
-    a.shift = shift; a.has_shift = 1;
-    {   // the sets stay in the Infinity Cache when they (and the matrix, if it is not in LDS) fit half of it
-        const double ws = 16.0 * (double)nsig * (double)st + (a.mat_entries ? 0.0 : (double)c->matrix_bytes);
-        a.set_nt = ws > 0.5 * 256.0 * 1048576.0;
-        if (const char *e = knob_x("BICG_SHP_NT")) a.set_nt = atoi(e) != 0;
-    }
-    a.timeout_ticks = c->p2p ? c->p2p->timeout_ticks : 200000000ull;
-    static const int xcd_map = knob_x("BICG_PERSIST_XCD") ? atoi(knob_x("BICG_PERSIST_XCD")) : 1;
-    a.xcd_map = xcd_map;
-    static const int first_sleep = knob_x("BICG_PERSIST_SLEEP") ? atoi(knob_x("BICG_PERSIST_SLEEP")) : 1;
-    a.first_sleep = (unsigned)first_sleep;
-    if (!pipe) c->persist_seq += 3u * (unsigned)niter;
-    if (a.multi) {
-        a.halo_seq0 = c->halo_seq;
-        a.p2p = c->p2p->red_desc(c->p2p->red_seq);
-        if (!pipe) { c->halo_seq += 2u * (unsigned)niter; c->p2p->red_seq += 3u * (unsigned)niter; }
-        a.ring = c->halo_ring;
-        c->halo_unsynced = 0;
-    }
-    const hipError_t err = pipe ? launch_shpipe_persist(a, c->sc) : launch_shlop_persist(a, c->sc);
-    if (err != hipSuccess) {
-        if (c->nranks > 1) die("persistent kernel", "launch failed on a multi-rank run (BICG_PERSIST=0 selects the multi-launch iteration)");
-        fprintf(stderr, "bicgstab_hip: falling back to the multi-launch iteration\n");
-        return false;
-    }
-    return true;
-}
-
-// after a pipelined persistent launch (fetch_scal has brought the scalar block back): advance the sequence counters by what
-// the launch consumed. Identical on every rank -- the decisions inside the launch depend on globally reduced sums only.
-void persist_account(bicg_ctx *c)
-{
-    const unsigned nv = (unsigned)c->hS->red[kRedUsedV], ng = (unsigned)c->hS->red[kRedUsedG];
-    c->persist_seq += ng;
-    c->persist_vseq += nv;
-    if (!c->single()) { c->halo_seq += nv; c->p2p->red_seq += ng; }
-    c->adaptive_rr += (int)c->hS->red[kRedAdaptive];
-}
 
 // vectors, reduction scratch and scalar blocks of a context whose plan (n_loc, halo, nblk) is known
 static void ctx_state(bicg_ctx *c, Comm *comm, uint32_t ngroups)
@@ -588,6 +460,272 @@ static void preload_for(bicg_ctx *c)
     if (c->lane_info && c->jagw_fast) preload_jagw_kernels();
 }
 
+// switches both constructors read into the context
+static void ctx_read_switches(bicg_ctx *c)
+{
+    if (const char *sv = knob_x("BICG_SELL_NT")) c->sell_nt_env = atoi(sv);
+    if (const char *sv = knob_x("BICG_SELL_ALT")) c->sell_alt = atoi(sv);
+    if (const char *sv = knob_x("BICG_SELL_XCD")) c->sell_xcd = atoi(sv);
+    if (const char *sv = test_tok("force-comm")) c->force_comm = atoi(sv) != 0;
+}
+
+// what the halo plan leaves on the host for the later stages (uploads, the persistent plan, the transport)
+namespace {
+struct HaloHost {
+    std::vector<uint32_t> ocol, optr, send_idx;
+    std::vector<double> oval;
+    std::vector<unsigned long long> dst0, dstride;      // p2p_transport: where every entry of the send list lands, and its slot size
+};
+}  // namespace
+
+// The common tail of both constructors: vectors and scalar blocks, the form of the pipelined iteration, what every rank must
+// agree on, the persistent plan (host: the blocks bicg_create was given; null: none), streams, code objects.
+static void ctx_finish(bicg_ctx *c, Comm *comm, uint32_t ngroups, const CSR_Matrix *diag, const HaloHost *host, PlanTrace &trace)
+{
+    ctx_state(c, comm, ngroups);
+    if (const char *sv = test_tok("spin-ticks")) c->spin_ticks = strtoull(sv, nullptr, 10);
+    // Round 4: with the products alternating direction and reading no column index in uniform slices, a big block is faster
+    // as two plain products + two element-wise kernels (Transport-shaped, one GPU: 139.0 vs 152.0 us per pipelined iteration;
+    // profiles/NOTES.md): the fused two-launch form stays what it was built for -- the latency-bound ranks.
+    c->fuse_pipe = c->fuse_small;
+    if (const char *sv = plan_tok("fuse-pipe")) c->fuse_pipe = atoi(sv) != 0;
+    else if (const char *pv = plan_tok("pipe-probe")) c->pipe_probe = atoi(pv);
+    c->spmm_ok = all_ranks(comm, spmm_possible(c));
+    c->fuse_plan_ok = all_ranks(comm, c->glist_all && c->nblk == 0 && (c->single() || (c->p2p && c->ll_fused)));
+    BICG_HIP(hipHostMalloc((void **)&c->hS, sizeof(Scal), hipHostMallocDefault));
+    memset(c->hS, 0, sizeof(Scal));
+    if (host) {   // persistent pipelined iteration for latency-bound ranks: available when the plan fits on EVERY rank
+        const bool off = knob_tok("BICG_PERSIST", "0") || knob_tok("BICG_PERSIST", "off");
+        bool mine = !off && persist_build(c, diag, host->optr, host->ocol, host->oval, host->send_idx, host->dst0, host->dstride);
+        c->persist_on = all_ranks(comm, mine);
+        if (const char *pp = knob_x("BICG_PERSIST_PLAIN")) c->persist_plain = atoi(pp) != 0;
+        if (!c->persist_on && mine) { for (void *p : c->persist_mem) (void)hipFree(p); c->persist_mem.clear(); c->persist = PersistArgs{}; }
+    }
+    trace.mark("transport, persistent plan");
+    ctx_streams(c, c->nranks);
+    trace.mark("streams");
+    preload_for(c);
+    trace.mark("code objects");
+}
+
+// Every rank learns every rank's (non-zeros, rows). The enqueue mode changes the ORDER of RCCL calls,
+// so all ranks must take the same decision: it is based on the average number of local non-zeros.
+// (a rank without rows carries a phantom row and counts as a rank like any other; only an EMPTY MATRIX is refused: false)
+static bool shared_facts(bicg_ctx *c, Comm *comm, const INFO_Matrix *info, PlanFacts &facts)
+{
+    const int P = c->nranks;
+    uint64_t total = c->nnz_d;
+    bool empty = c->n_loc == 0;
+    if (P > 1) {
+        std::vector<int> cnt(P, 2 * (int)sizeof(uint32_t)), off(P);
+        std::vector<uint32_t> mine(2 * (size_t)P), all(2 * (size_t)P, 0u);
+        for (int p = 0; p < P; ++p) { off[p] = 2 * p * (int)sizeof(uint32_t); mine[2 * p] = c->nnz_d; mine[2 * p + 1] = c->n_loc; }
+        comm->alltoallv_host(mine.data(), cnt.data(), off.data(), all.data(), cnt.data(), off.data());
+        all[2 * c->rank] = c->nnz_d; all[2 * c->rank + 1] = c->n_loc;
+        total = 0;
+        for (int p = 0; p < P; ++p) { total += all[2 * p]; empty = empty || all[2 * p + 1] == 0; }
+    }
+    if (empty) {
+        if (c->rank == 0) fprintf(stderr, "ERROR: bicg_create: empty matrix (%u rows over %d ranks)\n", info->rows, P);
+        return false;
+    }
+    c->overlap = total / (uint64_t)P >= 6000000u;
+    // two launches per pipelined iteration (phases in the SpMV epilogues): latency on small ranks (200 k rows 26.2
+    // vs 34.1 us), the traffic of v and t on large ones (1.6 M rows 159 vs 163 us, banded b = 8 158 vs 169, the
+    // 16.8 M-row Laplacian share 1.14 vs 1.25 ms) -- except with x windows, whose epilogue kernels at 4 waves per
+    // SIMD lose on large blocks (FEM-like 189 vs 175 us). Like the enqueue mode this changes the sequence of
+    // exchanges, so it is decided from facts all ranks share (see fuse_plan_ok), never from the local block alone.
+    c->fuse_small = total / (uint64_t)P < 6000000u;
+    facts.P = P; facts.rows_global = info->rows; facts.nnz_diag_all = total; facts.fuse_small = c->fuse_small;
+    return true;
+}
+
+// ---- halo plan (multi rank): which of x's remote entries this rank needs, who needs ours
+static void halo_plan(bicg_ctx *c, Comm *comm, const CSR_Matrix *offd, const INFO_Matrix *info, HaloHost &h)
+{
+    const int P = c->nranks;
+    h.optr.assign(c->n_loc + 1, 0u);
+    c->scnt.assign(P, 0); c->sdsp.assign(P, 0); c->rcnt.assign(P, 0); c->rdsp.assign(P, 0);
+    if (P == 1) return;
+    if (offd->rows != c->n_loc) die("bicg_create", "offd block row count differs from diag block");
+    c->nnz_o = offd->ptr[offd->rows];
+    std::vector<uint32_t> halo_cols(c->nnz_o ? c->nnz_o : 1);
+    h.ocol.resize(c->nnz_o ? c->nnz_o : 1);
+    c->halo = (uint32_t)bicg_halo_plan(offd, info, P, c->n_loc, halo_cols.data(), c->rcnt.data(), h.ocol.data());
+    h.optr.assign(offd->ptr, offd->ptr + c->n_loc + 1);
+    h.oval.assign(offd->val, offd->val + c->nnz_o);
+    for (int p = 1; p < P; ++p) c->rdsp[p] = c->rdsp[p - 1] + c->rcnt[p - 1];
+    // tell every owner which of its rows we need; learn which of ours the others need
+    auto tramp = [](const void *sbuf, const int *sc, const int *sd, void *rbuf, const int *rc, const int *rd, void *user) {
+        static_cast<Comm *>(user)->alltoallv_host(sbuf, sc, sd, rbuf, rc, rd);
+    };
+    const int total = bicg_halo_send_counts(P, c->rcnt.data(), tramp, comm, c->scnt.data());
+    h.send_idx.resize(total > 0 ? total : 1);
+    const int got = bicg_halo_send_lists(c->rank, P, info, c->n_loc, halo_cols.data(), c->rcnt.data(), c->scnt.data(),
+                                         tramp, comm, h.send_idx.data());
+    if (got < 0) die("bicg_create", "halo request outside the owner's rows");
+    c->nsend = (uint32_t)got;
+    for (int p = 1; p < P; ++p) c->sdsp[p] = c->sdsp[p - 1] + c->scnt[p - 1];
+}
+
+// The only place that turns the plan of the diag block (sell_plan_host, bicg_sell_plan.cpp) into device memory, and the one
+// place that adds up the bytes of the matrix.
+// Only what some kernel reads goes to the GPU: the CSR val/col arrays when there are row blocks for the
+// CSR kernel (none for banded matrices: everything is on the sliced-ELL path), the 32-bit sliced-ELL
+// columns when the 16-bit offsets do not apply. (Round 1 kept all of them: 2.3 x the matrix.)
+// (The offd block and the send list of the halo plan go up from here too, where they always have: the order of the allocations,
+// and with it every device address, is the same from build to build, so timings of two builds stay comparable.)
+static void sell_plan_upload(bicg_ctx *c, const CSR_Matrix *diag, const SellPlan &p, const PlanSwitches &sw, const HaloHost &h)
+{
+    const uint32_t nrows = p.nrows, nslices = p.nslices;
+    const uint64_t sell_entries = p.sell_entries;
+    const bool c16 = p.c16, csr16 = p.csr16;
+    c->rowsplit = p.rowsplit; c->fw = p.fw;
+    c->sell_entries = sell_entries; c->sell_nnz = p.sell_nnz; c->sell_rows = p.sell_rows;
+    c->sell_jag = p.jag && sell_entries > 0;
+    c->uniform_entries = p.uniform_entries; c->constant_entries = p.constant_entries; c->masked_rows = p.masked_rows;
+    c->n_int = (uint32_t)p.bint.size(); c->n_bnd = (uint32_t)p.bbnd.size();
+    c->nblk = c->n_int + c->n_bnd;
+    c->ng_int = (uint32_t)p.gl_int.size(); c->ng_bnd = (uint32_t)p.gl_bnd.size();
+    c->glist_int_identity = c->ng_int == p.ngroups;     // every group, in order: index directly
+    c->glist_all = c->ng_int + c->ng_bnd == p.ngroups;
+    const bool need_csr = c->nblk > 0;
+    c->d_val = dev_upload_padded(diag->val, need_csr ? c->nnz_d : 0, kPadEntries);
+    c->d_col = dev_upload_padded(diag->col, need_csr && !csr16 ? c->nnz_d : 0, kPadEntries);
+    if (csr16) c->d_col16 = dev_upload(p.dcol16.data(), p.dcol16.size());
+    c->d_ptr = dev_upload(diag->ptr, (size_t)c->n_loc + 1);
+    c->o_val = dev_upload(h.oval.data(), c->nnz_o);
+    c->o_col = dev_upload(h.ocol.data(), c->nnz_o);
+    c->o_ptr = dev_upload(h.optr.data(), (size_t)c->n_loc + 1);
+    c->desc_int = dev_upload(p.bint.data(), p.bint.size());
+    c->desc_bnd = dev_upload(p.bbnd.data(), p.bbnd.size());
+    // (jagged slices: lanes whose row has ended read up to one entry past the last -- kPadEntries of slack)
+    c->s_val = dev_upload_padded(p.sval.get(), (size_t)sell_entries, kPadEntries);
+    c->s_col = dev_upload_padded(p.scol.get(), c16 ? 0 : (size_t)sell_entries, kPadEntries);
+    if (!p.vbase.empty()) {
+        c->s_vbase = dev_upload(p.vbase.data(), p.vbase.size());
+        c->s_uval = dev_upload(p.uval.data(), p.uval.size());
+    }
+    if (!p.mbase.empty()) {
+        c->s_mbase = dev_upload(p.mbase.data(), p.mbase.size());
+        c->s_rmask = dev_upload(p.rmask.data(), p.rmask.size());
+    }
+    if (!p.ubase.empty()) {
+        c->s_ubase = dev_upload(p.ubase.data(), p.ubase.size());
+        c->s_uoff = dev_upload(p.uoff.data(), p.uoff.size());
+    }
+    build_slice_desc(c, nslices, nrows, p.slice_len.data(), p.ubase, p.vbase, p.mbase, p.uoff, p.uval, p.rmask.empty() ? nullptr : p.rmask.data());
+    if (c16) {
+        c->s_col16 = dev_upload_padded(p.scol16.get(), p.n16_alloc(), kPadEntries);
+        c->s_base16 = dev_upload(p.slice_base16.data(), p.slice_base16.size());
+    }
+    if (p.win) {
+        c->win_ptr = dev_upload(p.win_ptr.data(), p.win_ptr.size());
+        c->win_runs = dev_upload(p.win_runs.data(), p.win_runs.size());
+        c->win_slots = p.win_slots; c->win_max_runs = p.win_max_runs; c->win_near16 = p.win_near16;
+        if (p.win_list_mode) {
+            c->win_list = dev_upload(p.list.data(), p.list.size());
+            c->win_lptr = dev_upload(p.lptr.data(), p.lptr.size());
+            c->win_ltotal = dev_upload(p.total.data(), p.total.size());
+        }
+        if (!p.perm.empty()) c->sell_perm = dev_upload(p.perm.data(), p.perm.size());
+    }
+    if (p.jag && sell_entries > 0) {
+        c->jag_tail16_max = p.jag_tail16_max;
+        if (!p.lane_info.empty()) c->lane_info = dev_upload(p.lane_info.data(), p.lane_info.size());
+        if (sw.jagw >= 0) c->jagw_fast = sw.jagw != 0;
+    }
+    c->s_base = dev_upload(p.slice_base.data(), p.slice_base.size());
+    c->s_len = dev_upload(p.slice_len.data(), p.slice_len.size());
+    c->glist_int = dev_upload(p.gl_int.data(), p.gl_int.size());
+    c->glist_bnd = dev_upload(p.gl_bnd.data(), p.gl_bnd.size());
+    c->send_idx = dev_upload(h.send_idx.data(), c->nsend);
+    c->sendbuf = dev_alloc<double>(c->nsend);
+
+    // ---- bytes. matrix_bytes: what one SpMV streams from the matrix arrays; device_matrix_bytes: what is resident.
+    const uint64_t ptr_bytes = 4ull * (nrows + 1);
+    const uint64_t list_bytes = p.win && p.win_list_mode ? 4ull * p.list.size() + 8ull * p.lptr.size() : 0ull;
+    const uint64_t run_bytes = p.win ? 4ull * p.win_ptr.size() + 8ull * p.win_runs.size() : 0ull;
+    const uint64_t lane_bytes = c->lane_info ? 2ull * p.lane_info.size() : 0ull;
+    // (16 bytes of descriptor per slice where base + length were counted; the list-driven product reads the list, not the runs)
+    const uint64_t streamed = (uint64_t)sell_entries * (c16 ? 10 : 12) - p.uniform_entries * (c16 ? 2 : 4) - p.constant_entries * 8ull + 2ull * p.masked_rows +
+                              8ull * nslices + ptr_bytes + (uint64_t)(c->nnz_d - c->sell_nnz) * (csr16 ? 10 : 12) + (uint64_t)c->nnz_o * 12 +
+                              (c->s_desc ? 8ull * nslices : 0ull) + list_bytes + (p.win_list_mode ? 0ull : run_bytes) + lane_bytes;
+    // (one rank: every product goes through the three-trip kernels, which do not read the row pointers)
+    c->matrix_bytes = streamed - (c->lane_info && c->nranks == 1 && streamed > ptr_bytes ? ptr_bytes : 0ull);
+    c->device_matrix_bytes = (need_csr ? (csr16 ? 10ull : 12ull) * c->nnz_d : 0ull) + 4ull * (c->n_loc + 1) + 12ull * c->nnz_o + 4ull * (c->n_loc + 1) +
+                             8ull * sell_entries + (c16 ? 2ull * p.n16 : 4ull * sell_entries) + 12ull * nslices + list_bytes + run_bytes + lane_bytes;
+}
+
+// Across ranks (a z-slab of BASELINE.json configs[3]: 64 planes of 512^2 per GPU) the plane-marching product takes the
+// planes without halo entries; the halo-touching planes go through the slice-by-slice kernel behind the exchange. That
+// needs the two sets to BE whole planes: every group of a plane with a halo-touching group is halo-touching, and the
+// others form one range of planes. (Collective.)
+static void stencil_across_ranks(bicg_ctx *c, Comm *comm, const std::vector<uint32_t> &gl_bnd)
+{
+    const uint32_t gpp = (c->st.on && c->st.sz % kGroupRows == 0) ? c->st.sz / kGroupRows : 0u;
+    std::vector<char> bnd_plane(c->st.on ? c->st.nz : 1u, 0);
+    bool ok = gpp > 0 && c->glist_all && c->nblk == 0;
+    for (uint32_t g : gl_bnd) if (ok) bnd_plane[(size_t)g / gpp] = 1;
+    uint32_t nb = 0, lo = c->st.nz, hi = 0;
+    for (uint32_t z = 0; ok && z < c->st.nz; ++z) { if (bnd_plane[z]) ++nb; else { lo = std::min(lo, z); hi = std::max(hi, z + 1); } }
+    ok = ok && (uint64_t)nb * gpp == gl_bnd.size() && lo < hi;
+    for (uint32_t z = lo; ok && z < hi; ++z) ok = !bnd_plane[z];
+    ok = all_ranks(comm, ok);       // (every rank takes the same form of the exchange: collective)
+    if (ok) { c->st.z_lo = lo; c->st.z_hi = hi; c->st_multi = true; }
+    if (plan_trace_env() && c->rank == 0)
+        fprintf(stderr, "bicgstab_hip: plane-marching product across ranks: %s (planes %u .. %u of %u without halo entries)\n", ok ? "yes" : "no", lo, hi, c->st.nz);
+}
+
+// ---- peer-to-peer transport: publish this rank's halo landing ring, learn where every entry
+// of the send list lands in the ring of the rank that needs it (collective), and decide whether the exchange rides inside
+// the product's launch
+static void p2p_transport(bicg_ctx *c, Comm *comm, const SellPlan &plan, HaloHost &h)
+{
+    const int P = c->nranks;
+    c->p2p = comm->p2p;
+    if (const char *sv = test_tok("p2p-fault-after")) c->fault_after = atoi(sv);
+    // in-kernel collect needs the HEAVY kernel instantiations (occupancy 5 instead of 8 waves per SIMD,
+    // ~3 % per SpMV): worth it unless the local problem is so large that 3 % exceeds the ~10 us per
+    // iteration the separate apply kernels cost
+    c->inline_apply = c->nnz_d < 40000000u;
+    if (const char *sv = knob_x("BICG_P2P_INLINE_APPLY")) c->inline_apply = atoi(sv) != 0;
+    if (!(c->p2p && !c->single())) { c->p2p = nullptr; return; }
+    c->halo_ring = (llword *)c->p2p->alloc(sizeof(llword) * 2 * (size_t)kHaloRing * c->halo);
+    std::vector<void *> rings;
+    if (c->p2p->share(c->halo_ring, rings, c->ring_mapped) != 0)
+        die("bicg_create", "could not map the halo rings of the other ranks (peer-to-peer transport)");
+    // to rank p: where ITS values land in my ring, and my ring's slot size
+    std::vector<int> mine(2 * (size_t)P), theirs(2 * (size_t)P, 0), cnt(P, 2 * (int)sizeof(int)), dsp(P);
+    for (int p = 0; p < P; ++p) {
+        mine[2 * p] = c->rdsp[p]; mine[2 * p + 1] = (int)c->halo;
+        dsp[p] = 2 * p * (int)sizeof(int);
+    }
+    comm->alltoallv_host(mine.data(), cnt.data(), dsp.data(), theirs.data(), cnt.data(), dsp.data());
+    h.dst0.assign(c->nsend ? c->nsend : 1, 0ull); h.dstride.assign(c->nsend ? c->nsend : 1, 0ull);
+    for (int p = 0; p < P; ++p)
+        for (int j = 0; j < c->scnt[p]; ++j) {
+            const size_t i = (size_t)c->sdsp[p] + j;
+            h.dst0[i] = (unsigned long long)(uintptr_t)rings[p] + 16ull * ((unsigned long long)theirs[2 * p] + j);
+            h.dstride[i] = 16ull * (unsigned long long)theirs[2 * p + 1];
+        }
+    c->push_dst0 = dev_upload(h.dst0.data(), h.dst0.size());
+    c->push_stride = dev_upload(h.dstride.data(), h.dstride.size());
+    c->ll_fused = c->n_bnd == 0 && c->ng_int + c->ng_bnd > 0;
+    // Ragged rows (jagged slices): the launch with the exchange inside runs k_spmv_sell's loop over EVERY group, the rank's
+    // halo-free groups included; as separate launches -- push, interior, unpack, boundary -- the interior goes through the
+    // three-trip products of bicg_jagw.hip. Worth two more launches when the interior is large (measured with two 800 k-row
+    // ranks of the RCM-numbered mesh matrix sharing a GPU: profiles/r06/ragged_ranks_fused_or_split.txt); BICG_PLAN="halo-fused=0|1" decides.
+    if (c->ll_fused && c->sell_jag && c->lane_info && c->jagw_fast && (uint64_t)c->nnz_d >= 4000000ull) c->ll_fused = false;
+    if (const char *sv = plan_tok("halo-fused")) c->ll_fused = c->n_bnd == 0 && c->ng_int + c->ng_bnd > 0 && atoi(sv) != 0;
+    if (const char *sv = knob_x("BICG_P2P_FUSED")) c->ll_fused = c->ll_fused && atoi(sv) != 0;
+    if (c->ll_fused) {
+        std::vector<uint32_t> order(plan.gl_int);
+        order.insert(order.end(), plan.gl_bnd.begin(), plan.gl_bnd.end());
+        c->glist_ll = dev_upload(order.data(), order.size());
+    }
+}
+
 bicg_ctx *bicg_create(const CSR_Matrix *diag, const CSR_Matrix *offd, const INFO_Matrix *info)
 {
     Comm *comm = comm_get();
@@ -610,770 +748,37 @@ bicg_ctx *bicg_create(const CSR_Matrix *diag, const CSR_Matrix *offd, const INFO
     }
     c->n_loc = diag->rows; c->n_glob = info->rows;
     c->nnz_d = diag->rows ? diag->ptr[diag->rows] : 0u;
-    const int P = c->nranks;
-
-    bool use_sell = !(knob_x("BICG_NO_SELL") && atoi(knob_x("BICG_NO_SELL")));
-    if (const char *sv = knob_x("BICG_SELL_NT")) c->sell_nt_env = atoi(sv);
-    if (const char *sv = knob_x("BICG_SELL_ALT")) c->sell_alt = atoi(sv);
-    if (const char *sv = knob_x("BICG_SELL_XCD")) c->sell_xcd = atoi(sv);
-    if (const char *sv = test_tok("force-comm")) c->force_comm = atoi(sv) != 0;
+    ctx_read_switches(c);
     if (const char *sv = getenv("BICG_GRAPH")) c->graph_mode = atoi(sv);
-    uint64_t nnz_diag_all = c->nnz_d;      // diag non-zeros of all ranks
-    {   // Every rank learns every rank's (non-zeros, rows). The enqueue mode changes the ORDER of RCCL calls,
-        // so all ranks must take the same decision: it is based on the average number of local non-zeros.
-        // (a rank without rows carries a phantom row and counts as a rank like any other; only an EMPTY MATRIX is refused)
-        uint64_t total = c->nnz_d;
-        bool empty = c->n_loc == 0;
-        if (P > 1) {
-            std::vector<int> cnt(P, 2 * (int)sizeof(uint32_t)), off(P);
-            std::vector<uint32_t> mine(2 * (size_t)P), all(2 * (size_t)P, 0u);
-            for (int p = 0; p < P; ++p) { off[p] = 2 * p * (int)sizeof(uint32_t); mine[2 * p] = c->nnz_d; mine[2 * p + 1] = c->n_loc; }
-            comm->alltoallv_host(mine.data(), cnt.data(), off.data(), all.data(), cnt.data(), off.data());
-            all[2 * c->rank] = c->nnz_d; all[2 * c->rank + 1] = c->n_loc;
-            total = 0;
-            for (int p = 0; p < P; ++p) { total += all[2 * p]; empty = empty || all[2 * p + 1] == 0; }
-        }
-        if (empty) {
-            if (c->rank == 0) fprintf(stderr, "ERROR: bicg_create: empty matrix (%u rows over %d ranks)\n", info->rows, P);
-            bicg_destroy(c);          // nothing is allocated yet; takes the context out of the registry of live ones
-            return nullptr;
-        }
-        nnz_diag_all = total;
-        c->overlap = total / (uint64_t)P >= 6000000u;
-        // two launches per pipelined iteration (phases in the SpMV epilogues): latency on small ranks (200 k rows 26.2
-        // vs 34.1 us), the traffic of v and t on large ones (1.6 M rows 159 vs 163 us, banded b = 8 158 vs 169, the
-        // 16.8 M-row Laplacian share 1.14 vs 1.25 ms) -- except with x windows, whose epilogue kernels at 4 waves per
-        // SIMD lose on large blocks (FEM-like 189 vs 175 us). Like the enqueue mode this changes the sequence of
-        // exchanges, so it is decided from facts all ranks share (see fuse_plan_ok), never from the local block alone.
-        c->fuse_small = total / (uint64_t)P < 6000000u;
+
+    // ---- facts shared by all ranks (collective)
+    PlanFacts facts;
+    if (!shared_facts(c, comm, info, facts)) {
+        bicg_destroy(c);          // nothing is allocated yet; takes the context out of the registry of live ones
+        return nullptr;
     }
     if (const char *sv = getenv("BICG_OVERLAP")) c->overlap = atoi(sv) != 0;
     if (const char *sv = knob_x("BICG_SELL_GPW")) c->sell_gpw = atoi(sv);
     if (const char *sv = knob_x("BICG_SELL_GPW_DOTS")) c->sell_gpw_dots = atoi(sv);
 
-    // ---- halo plan (multi rank): which of x's remote entries this rank needs, who needs ours
-    std::vector<uint32_t> ocol, optr(c->n_loc + 1, 0u);
-    std::vector<double> oval;
-    std::vector<uint32_t> send_idx;
-    c->scnt.assign(P, 0); c->sdsp.assign(P, 0); c->rcnt.assign(P, 0); c->rdsp.assign(P, 0);
-    if (P > 1) {
-        if (offd->rows != c->n_loc) die("bicg_create", "offd block row count differs from diag block");
-        c->nnz_o = offd->ptr[offd->rows];
-        std::vector<uint32_t> halo_cols(c->nnz_o ? c->nnz_o : 1);
-        ocol.resize(c->nnz_o ? c->nnz_o : 1);
-        c->halo = (uint32_t)bicg_halo_plan(offd, info, P, c->n_loc, halo_cols.data(), c->rcnt.data(), ocol.data());
-        optr.assign(offd->ptr, offd->ptr + c->n_loc + 1);
-        oval.assign(offd->val, offd->val + c->nnz_o);
-        for (int p = 1; p < P; ++p) c->rdsp[p] = c->rdsp[p - 1] + c->rcnt[p - 1];
-        // tell every owner which of its rows we need; learn which of ours the others need
-        auto tramp = [](const void *sbuf, const int *sc, const int *sd, void *rbuf, const int *rc, const int *rd, void *user) {
-            static_cast<Comm *>(user)->alltoallv_host(sbuf, sc, sd, rbuf, rc, rd);
-        };
-        const int total = bicg_halo_send_counts(P, c->rcnt.data(), tramp, comm, c->scnt.data());
-        send_idx.resize(total > 0 ? total : 1);
-        const int got = bicg_halo_send_lists(c->rank, P, info, c->n_loc, halo_cols.data(), c->rcnt.data(), c->scnt.data(),
-                                             tramp, comm, send_idx.data());
-        if (got < 0) die("bicg_create", "halo request outside the owner's rows");
-        c->nsend = (uint32_t)got;
-        for (int p = 1; p < P; ++p) c->sdsp[p] = c->sdsp[p - 1] + c->scnt[p - 1];
-    }
+    HaloHost halo;
+    halo_plan(c, comm, offd, info, halo);
 
     // (BICG_PLAN_TRACE=1: seconds per part of the plan on stderr, rank 0)
-    const bool plan_trace = getenv("BICG_PLAN_TRACE") && atoi(getenv("BICG_PLAN_TRACE")) != 0 && comm->rank == 0;
-    double plan_t = now_sec();
-    auto plan_mark = [&](const char *what) {
-        if (!plan_trace) return;
-        const double t = now_sec();
-        fprintf(stderr, "bicgstab_hip: plan  %-34s %8.4f s\n", what, t - plan_t);
-        plan_t = t;
-    };
-    plan_mark("state, halo plan");
-    // ---- SpMV plan. Rows are cut into groups of 256 (4 slices of 64 rows = one workgroup, lane = row).
-    // Two layouts of a slice: PADDED to its longest row (banded matrices: nothing to pad, 8-byte loads of four
-    // 16-bit column offsets) or JAGGED (ragged rows: step k stores the rows longer than k only; exactly the CSR's
-    // bytes, lane = row kept). Jagged is chosen for the whole block when padding would add > 2 % entries. Groups
-    // with a very long row go to the CSR row-block kernel (strided workgroup reduction of one row). Either kind
-    // is "boundary" when one of its rows has offd entries (it then runs after the halo has landed).
-    const uint32_t nrows = c->n_loc;
-    const uint32_t nslices = (nrows + kSliceRows - 1) / kSliceRows, ngroups = (nrows + kGroupRows - 1) / kGroupRows;
-    // Long rows: lane = row needs 256 rows per workgroup, so a block of few, long rows (banded, half-bandwidth 512:
-    // 23 k rows of 1025 entries = 92 workgroups for 256 CUs) starves the GPU. Such a block goes to the rows-over-lanes
-    // kernel (k_spmv_rows) as a whole: row blocks of <= 8192 non-zeros, a row spread over 8..64 lanes. The row sums
-    // are then associated differently from mult() (tolerance 1e-13 x sum |a_ij x_j| instead of bit-exact).
-    // Decided from the GLOBAL shape (mean row length, rows per rank) so that all ranks agree.
-    {
-        const uint64_t mean_len = info->rows ? nnz_diag_all / info->rows : 0;     // (INFO_Matrix.nz is not always filled in)
-        const uint64_t groups_per_rank = ((uint64_t)info->rows / (uint64_t)P + kGroupRows - 1) / kGroupRows;
-        c->rowsplit = use_sell && (mean_len >= 256 || (mean_len >= 128 && groups_per_rank < 512));
-        if (const char *sv = knob_x("BICG_ROWSPLIT")) c->rowsplit = atoi(sv) != 0;
-        if (c->rowsplit) use_sell = false;
-    }
-    std::vector<uint32_t> slice_len(nslices, 0u), slice_base(nslices, 0u);
-    for (uint32_t r = 0; r < nrows; ++r)
-        slice_len[r / kSliceRows] = std::max(slice_len[r / kSliceRows], diag->ptr[r + 1] - diag->ptr[r]);
-    std::vector<uint32_t> gl_int, gl_bnd;
-    std::vector<uint4> bint, bbnd;
-    std::vector<char> group_is_sell(ngroups, 0);
-    const uint32_t jag_max_row = std::max<uint64_t>(64, nrows ? 4 * (uint64_t)c->nnz_d / nrows : 0);   // 4 x the average row
-    bool jag = false;
-    {
-        uint64_t padded_rows = 0;
-        for (uint32_t sl = 0; sl < nslices; ++sl)
-            padded_rows += (uint64_t)slice_len[sl] * std::min<uint32_t>(kSliceRows, nrows - sl * kSliceRows);
-        jag = padded_rows > (uint64_t)c->nnz_d + c->nnz_d / 50;
-        if (const char *sv = plan_tok("layout")) jag = !strcmp(sv, "jag") ? true : !strcmp(sv, "pad") ? false : jag;
-    }
-    // x windows in LDS (SellDev::win_*): wanted for ragged rows, where the x gather of one step touches many cache
-    // lines (FEM-like: 63 -> 58 us per SpMV). With equal rows the gathers are perfectly coalesced and the window
-    // only adds staging loads and two barriers per group (Transport-shaped +2 %, 256^3 Laplacian +9 % although its
-    // columns shrink from 32 to 16 bits), so there it is taken on request only: BICG_PLAN="window=1" asks for it
-    // whenever it fits, 0 never. It needs the jagged layout.
-    const bool jag_auto = jag;
-    int win_env = -1;
-    if (const char *sv = plan_tok("window")) win_env = atoi(sv);
-    bool want_win = use_sell && win_env != 0 && (win_env == 1 || jag_auto);
-    if (want_win) jag = true;
-    auto group_fits = [&](uint32_t g, uint64_t *stored_out) {
-        const uint32_t r0 = g * kGroupRows, r1 = std::min(nrows, r0 + kGroupRows);
-        const uint64_t nnz_g = diag->ptr[r1] - diag->ptr[r0];
-        if (jag) {
-            // a lane walks its row alone: an outlier row would keep its wavefront busy long after the launch's other
-            // rows are done, so it goes to the CSR kernel, which spreads one row over a workgroup
-            *stored_out = nnz_g;
-            for (uint32_t sl = r0 / kSliceRows; sl * kSliceRows < r1; ++sl)
-                if (slice_len[sl] > jag_max_row) return false;
-            return true;
-        }
-        // storage always covers 64 lanes per slice; the criterion only counts lanes that hold a row, so
-        // that the last, partly filled group of a block does not fall to the CSR kernel (an extra
-        // launch per SpMV for a few dozen rows)
-        uint64_t padded = 0, padded_rows = 0;
-        for (uint32_t sl = r0 / kSliceRows; sl * kSliceRows < r1; ++sl) {
-            padded += (uint64_t)slice_len[sl] * kSliceRows;
-            padded_rows += (uint64_t)slice_len[sl] * std::min<uint32_t>(kSliceRows, r1 - sl * kSliceRows);
-        }
-        *stored_out = padded;
-        return padded_rows <= nnz_g + nnz_g / 4 + 2 * kSliceRows;
-    };
-    // (Round 1, before the jagged layout: a ragged matrix left only a few groups under the padding limit; two
-    // kernels per SpMV were then slower than the CSR kernel alone -- synth.fem_like 70 vs 63 us -- and sorting rows
-    // by length inside the groups, SELL-C-sigma, removes the padding but also the coalesced x gather: 66.9 us.)
-    bool sell_worthwhile = use_sell;
-    uint64_t sell_entries = 0;
-    std::vector<uint32_t> win_ptr;
-    std::vector<uint2> win_runs;
-    uint32_t win_slots = 0;
-    bool win_list_mode = false;
-  select_groups:
-    sell_entries = 0; c->sell_nnz = 0; c->sell_rows = 0;
-    gl_int.clear(); gl_bnd.clear();
-    if (use_sell) {
-        uint64_t rows_fit = 0, dummy;
-        for (uint32_t g = 0; g < ngroups; ++g)
-            if (group_fits(g, &dummy)) rows_fit += std::min(nrows, (g + 1) * (uint32_t)kGroupRows) - g * kGroupRows;
-        sell_worthwhile = 2 * rows_fit >= nrows;
-    }
-    for (uint32_t g = 0; g < ngroups; ++g) {
-        const uint32_t r0 = g * kGroupRows, r1 = std::min(nrows, r0 + kGroupRows);
-        const uint64_t nnz_g = diag->ptr[r1] - diag->ptr[r0];
-        uint64_t stored = 0;
-        const bool sell = sell_worthwhile && group_fits(g, &stored) && sell_entries + stored < 0xFFFFFF00ull;
-        group_is_sell[g] = sell;
-        if (!sell) continue;
-        for (uint32_t sl = r0 / kSliceRows; sl * kSliceRows < r1; ++sl) {
-            slice_base[sl] = (uint32_t)sell_entries;
-            if (jag) sell_entries += diag->ptr[std::min(nrows, (sl + 1) * (uint32_t)kSliceRows)] - diag->ptr[sl * kSliceRows];
-            else sell_entries += (uint64_t)slice_len[sl] * kSliceRows;
-        }
-        c->sell_nnz += nnz_g; c->sell_rows += r1 - r0;
-        const bool touches_halo = P > 1 && optr[r1] > optr[r0];
-        (touches_halo ? gl_bnd : gl_int).push_back(g);
-    }
-    if (want_win) {
-        // per group: the columns its rows touch, merged into runs of consecutive columns (bicg_plan.cpp)
-        constexpr uint32_t kWinGap = 8;
-        bool ok = sell_entries > 0;
-        long nruns = ok ? bicg_window_plan(diag->ptr, diag->col, nrows, kGroupRows, group_is_sell.data(), kWinMaxSlots, kWinGap,
-                                           nullptr, nullptr, nullptr) : -1;
-        if (nruns >= 0) {
-            win_ptr.assign(ngroups + 1, 0u);
-            win_runs.assign((size_t)nruns + 1, make_uint2(0u, 0u));
-            static_assert(sizeof(uint2) == 2 * sizeof(unsigned int), "run = two 32-bit words");
-            bicg_window_plan(diag->ptr, diag->col, nrows, kGroupRows, group_is_sell.data(), kWinMaxSlots, kWinGap, win_ptr.data(),
-                             reinterpret_cast<unsigned int *>(win_runs.data()), &win_slots);
-        } else {
-            ok = false;
-        }
-        // The window pays through k_spmv_jagw only (three dependent trips per group, bicg_jagw.hip): at most kJagwMaxRuns runs per
-        // group and kJagwMaxSlots slots. A numbering whose groups touch MANY short runs (reverse Cuthill-McKee of a tetrahedral
-        // mesh: up to 170 runs, 2 657 slots) would go through k_spmv_sell's window loop, which stages run after run: 169 us per
-        // product on the 1.6 M-row mesh matrix against 56.5 us for the same jagged slices with 16-bit offsets gathered through
-        // the caches (profiles/r06/mesh_probe_baseline.txt, mesh_probe_plans.txt). Unless BICG_PLAN="window=1" insists, such a
-        // block keeps its jagged slices and drops the window.
-        if (ok && win_env != 1) {
-            uint32_t most_runs = 0;
-            for (uint32_t g = 0; g < ngroups; ++g) most_runs = std::max(most_runs, win_ptr[g + 1] - win_ptr[g]);
-            if (most_runs > kJagwMaxRuns || win_slots > kJagwMaxSlots) ok = false;
-            // ... unless the group's DISTINCT columns fit the window one by one (no gaps merged): the list-driven window of
-            // k_spmv_jagw<.., LIST> (SellDev::win_list). One rank only -- launches with offd entries or the exchange inside go
-            // through k_spmv_sell's loop, which would have to stage hundreds of runs -- and not for blocks whose pipelined
-            // phases ride in the products' epilogues (the same loop). BICG_PLAN="window-list=0" keeps the gathers.
-            if (!ok && P == 1 && !c->fuse_small && sell_entries > 0 && !plan_off("window-list")) {
-                long nr = bicg_window_plan(diag->ptr, diag->col, nrows, kGroupRows, group_is_sell.data(), kJagwMaxSlots, 0u, nullptr, nullptr, nullptr);
-                bool near = nr >= 0;
-                for (uint32_t g = 0; near && g < ngroups; ++g) {      // 16-bit list entries: distance from the group's first row
-                    if (!group_is_sell[g]) continue;
-                    const uint32_t r0 = g * kGroupRows, r1 = std::min(nrows, r0 + kGroupRows);
-                    for (uint32_t j = diag->ptr[r0]; j < diag->ptr[r1]; ++j) {
-                        const long d = (long)diag->col[j] - (long)r0;
-                        if (d < -32768 || d > 32767) { near = false; break; }
-                    }
-                }
-                if (near) {
-                    win_ptr.assign(ngroups + 1, 0u);
-                    win_runs.assign((size_t)nr + 1, make_uint2(0u, 0u));
-                    bicg_window_plan(diag->ptr, diag->col, nrows, kGroupRows, group_is_sell.data(), kJagwMaxSlots, 0u, win_ptr.data(),
-                                     reinterpret_cast<unsigned int *>(win_runs.data()), &win_slots);
-                    win_list_mode = true;
-                    ok = true;
-                }
-            }
-        }
-        if (!ok) {                          // some group's window does not fit: no windows for this block
-            want_win = false; win_slots = 0; win_runs.clear(); win_ptr.clear();
-            if (!jag_auto) { jag = false; std::fill(group_is_sell.begin(), group_is_sell.end(), 0); goto select_groups; }
-        }
-    }
-    const bool win = want_win && win_slots > 0;
-    auto slot_of = [&](uint32_t g, uint32_t col) -> uint32_t {
-        return bicg_window_slot(reinterpret_cast<const unsigned int *>(win_runs.data()), win_ptr[g], win_ptr[g + 1], col);
-    };
-    // With windows: deal the rows of every group to the lanes by decreasing length (SellDev::perm). The group's
-    // entries stay where they are as a whole; the slices inside it change length.
-    std::vector<unsigned char> perm;
-    if (win && !(knob_x("BICG_SELL_SORT") && atoi(knob_x("BICG_SELL_SORT")) == 0)) {
-        perm.assign((size_t)ngroups * kGroupRows, 0);
-        std::vector<uint32_t> slice_sum(nslices, 0u);             // entries of a slice after the rows were dealt out
-        parallel_ranges(ngroups, 64, [&](size_t ga, size_t gb, int) {
-            for (uint32_t g = (uint32_t)ga; g < (uint32_t)gb; ++g) {
-                unsigned char *pg = perm.data() + (size_t)g * kGroupRows;
-                for (uint32_t t = 0; t < kGroupRows; ++t) pg[t] = (unsigned char)t;
-                if (!group_is_sell[g]) continue;
-                const uint32_t r0 = g * kGroupRows;
-                auto len_of = [&](unsigned t) -> uint32_t { return r0 + t < nrows ? diag->ptr[r0 + t + 1] - diag->ptr[r0 + t] : 0u; };
-                std::stable_sort(pg, pg + kGroupRows, [&](unsigned char x, unsigned char y) { return len_of(x) > len_of(y); });
-                for (uint32_t w = 0; w < kGroupRows / kSliceRows; ++w) {
-                    const uint32_t sl = g * (kGroupRows / kSliceRows) + w;
-                    if (sl >= nslices) break;
-                    uint32_t longest = 0; uint64_t sum = 0;
-                    for (uint32_t l = 0; l < kSliceRows; ++l) { const uint32_t n = len_of(pg[w * kSliceRows + l]); longest = std::max(longest, n); sum += n; }
-                    slice_len[sl] = longest; slice_sum[sl] = (uint32_t)sum;
-                }
-            }
-        });
-        uint64_t at = 0;
-        for (uint32_t g = 0; g < ngroups; ++g) {
-            if (!group_is_sell[g]) continue;
-            for (uint32_t sl = g * (kGroupRows / kSliceRows); sl < std::min(nslices, (g + 1) * (kGroupRows / kSliceRows)); ++sl) { slice_base[sl] = (uint32_t)at; at += slice_sum[sl]; }
-        }
-        if (at != sell_entries) die("bicg_create", "internal: sorted slices do not add up");
-    }
-    auto row_of = [&](uint32_t sl, uint32_t lane) -> uint32_t {      // the row lane `lane` of slice `sl` works on
-        if (perm.empty()) return sl * kSliceRows + lane;
-        const uint32_t g = sl / (kGroupRows / kSliceRows), w = sl % (kGroupRows / kSliceRows);
-        return g * kGroupRows + perm[(size_t)g * kGroupRows + w * kSliceRows + lane];
-    };
-    plan_mark("groups, windows, row order");
-    c->sell_entries = sell_entries;
-    c->sell_jag = jag && sell_entries > 0;
-    // (allocated without a fill: the threads that write a slice also zero its padding -- 330 MB of zeros from one thread were a
-    // third of this part)
-    std::unique_ptr<double[]> sval_mem(new double[sell_entries ? sell_entries : 1]);
-    double *const sval = sval_mem.get();
-    std::unique_ptr<uint32_t[]> scol_mem;                          // filled once it is known whether the 32-bit columns are uploaded
-    // 16-bit column offsets when every sliced-ELL entry is within +-32767 of its row
-    bool c16 = sell_entries > 0 && (win || !plan_off("col16"));
-    std::vector<uint32_t> slice_base16(nslices, 0u);
-    uint64_t n16 = 0;
-    if (jag) n16 = sell_entries;
-    else
-        for (uint32_t sl = 0; sl < nslices; ++sl) {
-            slice_base16[sl] = (uint32_t)n16;
-            if (group_is_sell[sl / (kGroupRows / kSliceRows)]) n16 += (uint64_t)((slice_len[sl] + 3) / 4) * 4 * kSliceRows;
-        }
-    if (n16 >= 0xFFFFFF00ull) c16 = false;
-    std::vector<int> offsets_seen;          // distinct column offsets (col - row), while they stay few: the fused-window clusters
-    bool offsets_few = true;
-    if (c16 && !win) {
-        // row ranges on several threads, a map of the offsets seen per thread; merged below (ascending: the order does not matter,
-        // the clusters are formed from the sorted list)
-        std::vector<std::vector<unsigned char>> marks((size_t)plan_threads());
-        std::vector<char> bad((size_t)plan_threads(), 0);
-        const int np = parallel_ranges(nrows, 4096, [&](size_t ra, size_t rb, int part) {
-            std::vector<unsigned char> &mark = marks[(size_t)part];
-            mark.assign(65536, 0);
-            for (uint32_t r = (uint32_t)ra; r < (uint32_t)rb && !bad[(size_t)part]; ++r) {
-                if (!group_is_sell[r / kGroupRows]) continue;
-                for (uint32_t j = diag->ptr[r]; j < diag->ptr[r + 1]; ++j) {
-                    const int64_t dlt = (int64_t)diag->col[j] - (int64_t)r;
-                    if (dlt < -32767 || dlt > 32767) { bad[(size_t)part] = 1; break; }
-                    mark[dlt + 32768] = 1;
-                }
-            }
-        });
-        for (int p = 0; p < np; ++p) if (bad[(size_t)p]) c16 = false;
-        for (int d = 0; c16 && d < 65536; ++d) {
-            bool any = false;
-            for (int p = 0; p < np && !any; ++p) any = marks[(size_t)p][(size_t)d] != 0;
-            if (!any) continue;
-            if (offsets_seen.size() >= 4096) { offsets_few = false; break; }
-            offsets_seen.push_back(d - 32768);
-        }
-    }
-    // Fused-window clusters (struct FusedWindow): the offsets fall into <= 4 clusters (gaps of more than 512 columns separate
-    // them) and a group's window -- 256 + span columns per cluster -- fits 2048 LDS slots. Padded slices with 16-bit offsets,
-    // every row on the sliced-ELL path. (The fused product itself is a one-rank form; the windowed SpMM uses the clusters on every rank.)
-    if (c16 && !jag && !win && offsets_few && sell_entries > 0) {
-        offsets_seen.push_back(0);
-        std::sort(offsets_seen.begin(), offsets_seen.end());
-        FusedWindow f{};
-        int ncl = 0, slots = 0;
-        bool ok = true;
-        for (size_t i = 0; i < offsets_seen.size() && ok;) {
-            size_t k = i;
-            while (k + 1 < offsets_seen.size() && offsets_seen[k + 1] - offsets_seen[k] <= 512) ++k;
-            if (ncl == kFwMaxClusters) { ok = false; break; }
-            f.lo[ncl] = offsets_seen[i]; f.hi[ncl] = offsets_seen[k];
-            f.bias[ncl] = slots - f.lo[ncl];
-            slots += kGroupRows + f.hi[ncl] - f.lo[ncl];
-            ++ncl;
-            i = k + 1;
-        }
-        if (ok && slots <= 2048) { f.ncl = ncl; f.slots = (unsigned)slots; c->fw = f; }
-    }
-    plan_mark("column offsets, clusters");
-    const size_t n16_alloc = c16 ? (size_t)n16 : 1;
-    std::unique_ptr<short[]> scol16_mem(new short[n16_alloc]);
-    short *const scol16 = scol16_mem.get();
-    if (!c16) { scol16[0] = 0; scol_mem.reset(new uint32_t[sell_entries ? sell_entries : 1]); }
-    uint32_t *const scol = scol_mem.get();                        // null with 16-bit offsets: the 32-bit columns are not uploaded
-    if (sell_entries == 0) { sval[0] = 0.0; if (scol) scol[0] = 0u; }
-    // Slices on several threads: a slice's entries (and its padding, zeros) are its own range of the arrays.
-    parallel_ranges(nslices, 256, [&](size_t sa, size_t sb, int) {
-        for (uint32_t sl = (uint32_t)sa; sl < (uint32_t)sb; ++sl) {
-            const uint32_t g = sl / (kGroupRows / kSliceRows);
-            if (!group_is_sell[g]) continue;
-            if (jag) {
-                size_t e = slice_base[sl];
-                for (uint32_t k = 0; k < slice_len[sl]; ++k)
-                    for (uint32_t lane = 0; lane < kSliceRows; ++lane) {
-                        const uint32_t r = row_of(sl, lane);
-                        if (r >= nrows || diag->ptr[r + 1] - diag->ptr[r] <= k) continue;
-                        const uint32_t j = diag->ptr[r] + k;
-                        sval[e] = diag->val[j];
-                        if (scol) scol[e] = diag->col[j];
-                        if (win) scol16[e] = (short)(unsigned short)slot_of(g, diag->col[j]);
-                        else if (c16) scol16[e] = (short)((int64_t)diag->col[j] - (int64_t)r);
-                        ++e;
-                    }
-                continue;
-            }
-            const size_t b0 = slice_base[sl], n = (size_t)slice_len[sl] * kSliceRows;
-            std::fill(sval + b0, sval + b0 + n, 0.0);
-            if (scol) std::fill(scol + b0, scol + b0 + n, 0u);
-            if (c16) std::fill(scol16 + slice_base16[sl], scol16 + slice_base16[sl] + (size_t)((slice_len[sl] + 3) / 4) * 4 * kSliceRows, (short)0);
-            for (uint32_t lane = 0; lane < kSliceRows; ++lane) {
-                const uint32_t r = sl * kSliceRows + lane;
-                if (r >= nrows) break;
-                for (uint32_t j = diag->ptr[r], k = 0; j < diag->ptr[r + 1]; ++j, ++k) {
-                    const size_t e = b0 + (size_t)k * kSliceRows + lane;
-                    sval[e] = diag->val[j];
-                    if (scol) scol[e] = diag->col[j];
-                    if (c16) scol16[(size_t)slice_base16[sl] + ((size_t)(k / 4) * kSliceRows + lane) * 4 + (k % 4)] =
-                                 (short)((int64_t)diag->col[j] - (int64_t)r);
-                }
-            }
-        }
-    });
+    const char *tv = plan_trace_env();
+    PlanTrace trace(tv && atoi(tv) != 0 && comm->rank == 0);
+    trace.mark("state, halo plan");
 
-    plan_mark("sliced-ELL arrays");
-    // Uniform slices (SellDev::ubase): all 64 rows present, equally long, entry k at the same distance from its row in
-    // every row. Lists are shared between slices (a banded matrix has ONE for its whole interior) and padded with zeros.
-    std::vector<uint32_t> ubase, vbase, mbase;
-    std::vector<int> uoff;
-    std::vector<double> uval;
-    std::vector<unsigned short> rmask;
-    uint64_t uniform_entries = 0, constant_entries = 0, masked_rows = 0;
-    const bool want_constant = !plan_off("constant");
-    const bool want_masked = !plan_off("masked");
-    if (!jag && sell_entries > 0 && !plan_off("uniform")) {
-        ubase.assign(nslices, 0xFFFFFFFFu);
-        std::map<std::vector<int>, uint32_t> lists, vlists;
-        std::vector<int> cur, vkey;
-        // which slices are uniform (1) / uniform and constant (2): 64 rows x length comparisons per slice, on several threads; the
-        // lists themselves are numbered by the pass below, in slice order
-        std::vector<char> cls(nslices, 0);
-        parallel_ranges(nslices, 256, [&](size_t sa, size_t sb, int) {
-            for (uint32_t sl = (uint32_t)sa; sl < (uint32_t)sb; ++sl) {
-                if (!group_is_sell[sl / (kGroupRows / kSliceRows)] || (sl + 1) * kSliceRows > nrows || slice_len[sl] == 0) continue;
-                const uint32_t r0 = sl * kSliceRows, len = slice_len[sl], p0 = diag->ptr[r0];
-                bool uni = true;
-                for (uint32_t l = 0; l < kSliceRows && uni; ++l) uni = diag->ptr[r0 + l + 1] - diag->ptr[r0 + l] == len;
-                for (uint32_t l = 1; l < kSliceRows && uni; ++l)
-                    for (uint32_t k = 0; k < len; ++k)
-                        if ((int64_t)diag->col[diag->ptr[r0 + l] + k] - (int64_t)(r0 + l) != (int64_t)diag->col[p0 + k] - (int64_t)r0) { uni = false; break; }
-                if (!uni) continue;
-                bool con = want_constant;
-                for (uint32_t l = 1; l < kSliceRows && con; ++l) con = memcmp(diag->val + diag->ptr[r0 + l], diag->val + p0, sizeof(double) * len) == 0;
-                cls[sl] = con ? 2 : 1;
-            }
-        });
-        for (uint32_t sl = 0; sl < nslices; ++sl) {
-            if (!group_is_sell[sl / (kGroupRows / kSliceRows)] || (sl + 1) * kSliceRows > nrows || slice_len[sl] == 0) continue;
-            const uint32_t r0 = sl * kSliceRows, len = slice_len[sl];
-            const bool uni = cls[sl] != 0;
-            if (uni) {
-                cur.assign(len, 0);
-                for (uint32_t k = 0; k < len; ++k) cur[k] = (int)((int64_t)diag->col[diag->ptr[r0] + k] - (int64_t)r0);
-            }
-            if (!uni) {
-                // masked slice (SellDev::mbase): the rows are sub-sequences of one ascending list of <= 16 (distance, value) pairs
-                if (!want_constant || !want_masked) continue;
-                std::map<int, long long> un;                                      // distance -> value bits
-                bool ok = true;
-                for (uint32_t l = 0; l < kSliceRows && ok; ++l) {
-                    const uint32_t p0 = diag->ptr[r0 + l], p1 = diag->ptr[r0 + l + 1];
-                    ok = p1 > p0 && p1 - p0 <= 16u;
-                    for (uint32_t j = p0; j < p1 && ok; ++j) {
-                        if (j > p0 && diag->col[j] <= diag->col[j - 1]) { ok = false; break; }      // ascending columns
-                        const int d = (int)((int64_t)diag->col[j] - (int64_t)(r0 + l));
-                        long long b; memcpy(&b, diag->val + j, 8);
-                        auto f = un.find(d);
-                        if (f == un.end()) un.emplace(d, b); else ok = f->second == b;
-                    }
-                    ok = ok && un.size() <= 16u;
-                }
-                if (!ok) continue;
-                const uint32_t ulen = (uint32_t)un.size();
-                cur.clear(); vkey.clear();
-                std::vector<double> uv_list;
-                for (auto &kv : un) { cur.push_back(kv.first); double v; memcpy(&v, &kv.second, 8); uv_list.push_back(v); }
-                vkey.assign(cur.begin(), cur.end());
-                for (auto &kv : un) { vkey.push_back((int)(kv.second & 0xFFFFFFFF)); vkey.push_back((int)(kv.second >> 32)); }
-                auto it = lists.find(cur);
-                if (it == lists.end()) {
-                    if (uoff.size() + ulen + 32 > (1u << 24)) continue;
-                    it = lists.emplace(cur, (uint32_t)uoff.size()).first;
-                    uoff.insert(uoff.end(), cur.begin(), cur.end());
-                    uoff.resize((uoff.size() + 7) / 8 * 8 + 16, 0);
-                }
-                auto vt = vlists.find(vkey);
-                if (vt == vlists.end()) {
-                    if (uval.size() + ulen + 32 > (1u << 22)) continue;
-                    vt = vlists.emplace(vkey, (uint32_t)uval.size()).first;
-                    uval.insert(uval.end(), uv_list.begin(), uv_list.end());
-                    uval.resize((uval.size() + 7) / 8 * 8 + 16, 0.0);
-                }
-                if (vbase.empty()) vbase.assign(nslices, 0xFFFFFFFFu);
-                if (mbase.empty()) mbase.assign(nslices, 0xFFFFFFFFu);
-                ubase[sl] = it->second; vbase[sl] = vt->second;
-                mbase[sl] = (ulen << 26) | (uint32_t)(rmask.size() / kSliceRows);
-                for (uint32_t l = 0; l < kSliceRows; ++l) {
-                    unsigned m = 0;
-                    for (uint32_t j = diag->ptr[r0 + l]; j < diag->ptr[r0 + l + 1]; ++j) {
-                        const int d = (int)((int64_t)diag->col[j] - (int64_t)(r0 + l));
-                        m |= 1u << (unsigned)std::distance(un.begin(), un.find(d));
-                    }
-                    rmask.push_back((unsigned short)m);
-                }
-                uniform_entries += (uint64_t)len * kSliceRows; constant_entries += (uint64_t)len * kSliceRows;     // (padded entries the product no longer reads)
-                masked_rows += kSliceRows;
-                continue;
-            }
-            auto it = lists.find(cur);
-            if (it == lists.end()) {
-                if (uoff.size() + len + 32 > (1u << 24)) continue;            // the table stays small (scalar cache)
-                it = lists.emplace(cur, (uint32_t)uoff.size()).first;
-                uoff.insert(uoff.end(), cur.begin(), cur.end());
-                uoff.resize((uoff.size() + 7) / 8 * 8 + 16, 0);               // batches of up to 16 entries read past the list
-            }
-            ubase[sl] = it->second;
-            uniform_entries += (uint64_t)len * kSliceRows;
-            // constant slice: entry k holds the same value in all 64 rows (SellDev::vbase)
-            if (!want_constant) continue;
-            const double *v0 = diag->val + diag->ptr[r0];
-            if (cls[sl] != 2) continue;
-            vkey.assign(cur.begin(), cur.end());                                  // distances, then the value bits
-            for (uint32_t k = 0; k < len; ++k) { long long b; memcpy(&b, v0 + k, 8); vkey.push_back((int)(b & 0xFFFFFFFF)); vkey.push_back((int)(b >> 32)); }
-            auto vt = vlists.find(vkey);
-            if (vt == vlists.end()) {
-                if (uval.size() + len + 32 > (1u << 22)) continue;
-                vt = vlists.emplace(vkey, (uint32_t)uval.size()).first;
-                uval.insert(uval.end(), v0, v0 + len);
-                uval.resize((uval.size() + 7) / 8 * 8 + 16, 0.0);
-            }
-            if (vbase.empty()) vbase.assign(nslices, 0xFFFFFFFFu);
-            vbase[sl] = vt->second;
-            constant_entries += (uint64_t)len * kSliceRows;
-        }
-        if (uniform_entries == 0) { ubase.clear(); uoff.clear(); }
-    }
-    c->uniform_entries = uniform_entries;
-    c->constant_entries = constant_entries;
-    c->masked_rows = masked_rows;
+    // ---- the plan of the diag block, on the host, and its upload
+    const PlanSwitches sw = read_plan_switches();
+    SellPlan plan;
+    if (!sell_plan_host(diag, halo.optr.data(), facts, sw, plan, &trace)) die("bicg_create", "internal: sorted slices do not add up");
+    sell_plan_upload(c, diag, plan, sw, halo);
+    if (c->nranks > 1) stencil_across_ranks(c, comm, plan.gl_bnd);
+    trace.mark("upload");
 
-    plan_mark("uniform / constant / masked slices");
-    // CSR row blocks over the maximal runs of non-SELL groups
-    std::vector<uint32_t> rb(nrows + 1);
-    for (uint32_t g = 0; g < ngroups;) {
-        if (group_is_sell[g]) { ++g; continue; }
-        uint32_t g1 = g;
-        while (g1 < ngroups && !group_is_sell[g1]) ++g1;
-        const uint32_t r0 = g * kGroupRows, r1 = std::min(nrows, g1 * kGroupRows);
-        // bicg_row_blocks works on a ptr array that starts at the run's first row
-        const uint32_t nb = c->rowsplit ? bicg_row_blocks(diag->ptr + r0, r1 - r0, 8192, 256, rb.data())
-                                        : bicg_row_blocks(diag->ptr + r0, r1 - r0, kRowBlockNnz, 1024, rb.data());
-        for (uint32_t b = 0; b < nb; ++b) {
-            const uint32_t a0 = r0 + rb[b], a1 = r0 + rb[b + 1];
-            const bool touches_halo = P > 1 && optr[a1] > optr[a0];
-            (touches_halo ? bbnd : bint).push_back(make_uint4(a0, a1, diag->ptr[a0], diag->ptr[a1]));
-        }
-        g = g1;
-    }
-    c->n_int = (uint32_t)bint.size(); c->n_bnd = (uint32_t)bbnd.size();
-    c->nblk = c->n_int + c->n_bnd;
-    c->ng_int = (uint32_t)gl_int.size(); c->ng_bnd = (uint32_t)gl_bnd.size();
-    c->glist_int_identity = c->ng_int == ngroups;     // every group, in order: index directly
-    c->glist_all = c->ng_int + c->ng_bnd == ngroups;
-
-    plan_mark("row blocks");
-    // ---- upload
-    // Only what some kernel reads goes to the GPU: the CSR val/col arrays when there are row blocks for the
-    // CSR kernel (none for banded matrices: everything is on the sliced-ELL path), the 32-bit sliced-ELL
-    // columns when the 16-bit offsets do not apply. (Round 1 kept all of them: 2.3 x the matrix.)
-    const bool need_csr = c->nblk > 0;
-    bool csr16 = c->rowsplit && need_csr && !plan_off("col16");
-    std::vector<short> dcol16;
-    if (csr16) {                  // rows-over-lanes kernel: 16-bit column offsets in CSR order when every entry fits
-        dcol16.resize((size_t)c->nnz_d + kPadEntries, 0);
-        for (uint32_t r = 0; csr16 && r < nrows; ++r)
-            for (uint32_t j = diag->ptr[r]; j < diag->ptr[r + 1]; ++j) {
-                const int64_t dlt = (int64_t)diag->col[j] - (int64_t)r;
-                if (dlt < -32767 || dlt > 32767) { csr16 = false; break; }
-                dcol16[j] = (short)dlt;
-            }
-    }
-    c->d_val = dev_upload_padded(diag->val, need_csr ? c->nnz_d : 0, kPadEntries);
-    c->d_col = dev_upload_padded(diag->col, need_csr && !csr16 ? c->nnz_d : 0, kPadEntries);
-    if (csr16) c->d_col16 = dev_upload(dcol16.data(), dcol16.size());
-    c->d_ptr = dev_upload(diag->ptr, (size_t)c->n_loc + 1);
-    c->o_val = dev_upload(oval.data(), c->nnz_o);
-    c->o_col = dev_upload(ocol.data(), c->nnz_o);
-    c->o_ptr = dev_upload(optr.data(), (size_t)c->n_loc + 1);
-    c->desc_int = dev_upload(bint.data(), bint.size());
-    c->desc_bnd = dev_upload(bbnd.data(), bbnd.size());
-    // (jagged slices: lanes whose row has ended read up to one entry past the last -- kPadEntries of slack)
-    c->s_val = dev_upload_padded(sval, (size_t)sell_entries, kPadEntries);
-    c->s_col = dev_upload_padded(scol, c16 ? 0 : (size_t)sell_entries, kPadEntries);
-    c->matrix_bytes = (uint64_t)sell_entries * (c16 ? 10 : 12) - uniform_entries * (c16 ? 2 : 4) - constant_entries * 8ull + 2ull * masked_rows + 8ull * nslices + 4ull * (nrows + 1) +
-                      (uint64_t)(c->nnz_d - c->sell_nnz) * (csr16 ? 10 : 12) + (uint64_t)c->nnz_o * 12;
-    if (!vbase.empty()) {
-        c->s_vbase = dev_upload(vbase.data(), vbase.size());
-        c->s_uval = dev_upload(uval.data(), uval.size());
-    }
-    if (!mbase.empty()) {
-        c->s_mbase = dev_upload(mbase.data(), mbase.size());
-        c->s_rmask = dev_upload(rmask.data(), rmask.size());
-    }
-    if (!ubase.empty()) {
-        c->s_ubase = dev_upload(ubase.data(), ubase.size());
-        c->s_uoff = dev_upload(uoff.data(), uoff.size());
-    }
-    build_slice_desc(c, nslices, nrows, slice_len.data(), ubase, vbase, mbase, uoff, uval, rmask.empty() ? nullptr : rmask.data());
-    if (P > 1) {
-        // Across ranks (a z-slab of BASELINE.json configs[3]: 64 planes of 512^2 per GPU) the plane-marching product takes the
-        // planes without halo entries; the halo-touching planes go through the slice-by-slice kernel behind the exchange. That
-        // needs the two sets to BE whole planes: every group of a plane with a halo-touching group is halo-touching, and the
-        // others form one range of planes.
-        const uint32_t gpp = (c->st.on && c->st.sz % kGroupRows == 0) ? c->st.sz / kGroupRows : 0u;
-        std::vector<char> bnd_plane(c->st.on ? c->st.nz : 1u, 0);
-        bool ok = gpp > 0 && c->glist_all && c->nblk == 0;
-        for (uint32_t g : gl_bnd) if (ok) bnd_plane[(size_t)g / gpp] = 1;
-        uint32_t nb = 0, lo = c->st.nz, hi = 0;
-        for (uint32_t z = 0; ok && z < c->st.nz; ++z) { if (bnd_plane[z]) ++nb; else { lo = std::min(lo, z); hi = std::max(hi, z + 1); } }
-        ok = ok && (uint64_t)nb * gpp == gl_bnd.size() && lo < hi;
-        for (uint32_t z = lo; ok && z < hi; ++z) ok = !bnd_plane[z];
-        ok = all_ranks(comm, ok);       // (every rank takes the same form of the exchange: collective)
-        if (ok) { c->st.z_lo = lo; c->st.z_hi = hi; c->st_multi = true; }
-        if (getenv("BICG_PLAN_TRACE") && c->rank == 0)
-            fprintf(stderr, "bicgstab_hip: plane-marching product across ranks: %s (planes %u .. %u of %u without halo entries)\n", ok ? "yes" : "no", lo, hi, c->st.nz);
-    }
-    c->device_matrix_bytes = (need_csr ? (csr16 ? 10ull : 12ull) * c->nnz_d : 0ull) + 4ull * (c->n_loc + 1) + 12ull * c->nnz_o + 4ull * (c->n_loc + 1) +
-                             8ull * sell_entries + (c16 ? 2ull * n16 : 4ull * sell_entries) + 12ull * nslices;
-    if (c16) {
-        c->s_col16 = dev_upload_padded(scol16, n16_alloc, kPadEntries);
-        c->s_base16 = dev_upload(slice_base16.data(), slice_base16.size());
-    }
-    if (win) {
-        c->win_ptr = dev_upload(win_ptr.data(), win_ptr.size());
-        c->win_runs = dev_upload(win_runs.data(), win_runs.size());
-        c->win_slots = win_slots;
-        for (uint32_t g = 0; g < ngroups; ++g) c->win_max_runs = std::max(c->win_max_runs, win_ptr[g + 1] - win_ptr[g]);
-        c->win_near16 = true;
-        for (uint32_t g = 0; g < ngroups && c->win_near16; ++g)
-            for (uint32_t r = win_ptr[g]; r < win_ptr[g + 1]; ++r) {
-                const long lo = (long)win_runs[r].x - (long)(g * kGroupRows), hi = lo + (long)(win_runs[r].y & 0xFFFFu) - 1;
-                if (lo < -32767 || hi > 32767) { c->win_near16 = false; break; }
-            }
-        if (win_list_mode) {
-            // the runs spelled out, 16 bits per column (distance from the group's first row), two slots per word: word j of thread t
-            // (at lptr[g] + 256 j + t) holds slots t + 512 j (low half) and t + 512 j + 256 -- the slots thread t stages
-            std::vector<uint32_t> lptr(ngroups + 1, 0u);
-            std::vector<uint32_t> total(ngroups, 0u);
-            for (uint32_t g = 0; g < ngroups; ++g) {
-                uint32_t n = 0;
-                for (uint32_t r = win_ptr[g]; r < win_ptr[g + 1]; ++r) n += win_runs[r].y & 0xFFFFu;
-                total[g] = n;
-                lptr[g + 1] = lptr[g] + kGroupRows * ((n + 2u * kGroupRows - 1u) / (2u * kGroupRows));
-            }
-            std::vector<uint32_t> list((size_t)lptr[ngroups] + 8, 0u);
-            parallel_ranges(ngroups, 64, [&](size_t ga, size_t gb, int) {
-                for (uint32_t g = (uint32_t)ga; g < (uint32_t)gb; ++g) {
-                    uint32_t s = 0;
-                    for (uint32_t r = win_ptr[g]; r < win_ptr[g + 1]; ++r)
-                        for (uint32_t k = 0; k < (win_runs[r].y & 0xFFFFu); ++k, ++s) {
-                            const uint32_t d = (uint32_t)((int)(win_runs[r].x + k) - (int)(g * kGroupRows)) & 0xFFFFu;
-                            const uint32_t j = s / (2u * kGroupRows), rest = s % (2u * kGroupRows);
-                            uint32_t &w = list[(size_t)lptr[g] + (size_t)j * kGroupRows + rest % kGroupRows];
-                            w |= rest < kGroupRows ? d : d << 16;
-                        }
-                }
-            });
-            c->win_list = dev_upload(list.data(), list.size());
-            c->win_lptr = dev_upload(lptr.data(), lptr.size());
-            c->win_ltotal = dev_upload(total.data(), total.size());
-            c->device_matrix_bytes += 4ull * list.size() + 8ull * lptr.size();
-            c->matrix_bytes += 4ull * list.size() + 8ull * lptr.size();
-        }
-        if (!perm.empty()) c->sell_perm = dev_upload(perm.data(), perm.size());
-        c->device_matrix_bytes += 4ull * win_ptr.size() + 8ull * win_runs.size();
-        if (!win_list_mode) c->matrix_bytes += 4ull * win_ptr.size() + 8ull * win_runs.size();      // (the list-driven product reads the list, not the runs)
-    }
-    if (jag && sell_entries > 0) {
-    // (with or without a window: the three-trip products of bicg_jagw.hip read one word per lane instead of two row pointers)
-    // SellDev::lane_info: row in the group + its length per lane, in the order the lanes work (perm or natural)
-    {
-        std::vector<unsigned short> li((size_t)ngroups * kGroupRows, 0);
-        std::vector<char> too_long((size_t)plan_threads(), 0);
-        std::vector<uint32_t> tail_most((size_t)plan_threads(), 0u);      // entries behind the 16th of its rows, per slice (k_spmm_jpipe keeps them in LDS)
-        parallel_ranges(ngroups, 64, [&](size_t ga, size_t gb, int part) {
-            for (uint32_t g = (uint32_t)ga; g < (uint32_t)gb; ++g) {
-                uint32_t tail = 0;
-                for (uint32_t t = 0; t < kGroupRows; ++t) {
-                    const uint32_t in_group = perm.empty() ? t : perm[(size_t)g * kGroupRows + t], r = g * kGroupRows + in_group;
-                    const uint32_t n = (r < nrows && group_is_sell[g]) ? diag->ptr[r + 1] - diag->ptr[r] : 0u;
-                    if (n > 255u) too_long[(size_t)part] = 1;
-                    li[(size_t)g * kGroupRows + t] = (unsigned short)(in_group | (n << 8));
-                    if (t % kSliceRows == 0) tail = 0;
-                    tail += n > 16u ? n - 16u : 0u;
-                    tail_most[(size_t)part] = std::max(tail_most[(size_t)part], tail);
-                }
-            }
-        });
-        bool ok = true;
-        for (char b : too_long) ok = ok && !b;
-        for (uint32_t t : tail_most) c->jag_tail16_max = std::max(c->jag_tail16_max, t);
-        if (ok) {
-            c->lane_info = dev_upload(li.data(), li.size());
-            c->matrix_bytes += 2ull * li.size();
-            c->device_matrix_bytes += 2ull * li.size();
-            // (one rank: every product goes through the three-trip kernels, which do not read the row pointers)
-            if (P == 1 && c->matrix_bytes > 4ull * (nrows + 1)) c->matrix_bytes -= 4ull * (nrows + 1);
-        }
-        if (const char *v = plan_tok("jagw")) c->jagw_fast = atoi(v) != 0;
-    }
-    }
-    c->s_base = dev_upload(slice_base.data(), slice_base.size());
-    c->s_len = dev_upload(slice_len.data(), slice_len.size());
-    c->glist_int = dev_upload(gl_int.data(), gl_int.size());
-    c->glist_bnd = dev_upload(gl_bnd.data(), gl_bnd.size());
-    c->send_idx = dev_upload(send_idx.data(), c->nsend);
-    c->sendbuf = dev_alloc<double>(c->nsend);
-
-    plan_mark("upload");
-    // ---- peer-to-peer transport: publish this rank's halo landing ring, learn where every entry
-    // of the send list lands in the ring of the rank that needs it (collective)
-    c->p2p = comm->p2p;
-    std::vector<unsigned long long> dst0, dstride;
-    if (const char *sv = test_tok("p2p-fault-after")) c->fault_after = atoi(sv);
-    // in-kernel collect needs the HEAVY kernel instantiations (occupancy 5 instead of 8 waves per SIMD,
-    // ~3 % per SpMV): worth it unless the local problem is so large that 3 % exceeds the ~10 us per
-    // iteration the separate apply kernels cost
-    c->inline_apply = c->nnz_d < 40000000u;
-    if (const char *sv = knob_x("BICG_P2P_INLINE_APPLY")) c->inline_apply = atoi(sv) != 0;
-    if (c->p2p && !c->single()) {
-        c->halo_ring = (llword *)c->p2p->alloc(sizeof(llword) * 2 * (size_t)kHaloRing * c->halo);
-        std::vector<void *> rings;
-        if (c->p2p->share(c->halo_ring, rings, c->ring_mapped) != 0)
-            die("bicg_create", "could not map the halo rings of the other ranks (peer-to-peer transport)");
-        // to rank p: where ITS values land in my ring, and my ring's slot size
-        std::vector<int> mine(2 * (size_t)P), theirs(2 * (size_t)P, 0), cnt(P, 2 * (int)sizeof(int)), dsp(P);
-        for (int p = 0; p < P; ++p) {
-            mine[2 * p] = c->rdsp[p]; mine[2 * p + 1] = (int)c->halo;
-            dsp[p] = 2 * p * (int)sizeof(int);
-        }
-        comm->alltoallv_host(mine.data(), cnt.data(), dsp.data(), theirs.data(), cnt.data(), dsp.data());
-        dst0.assign(c->nsend ? c->nsend : 1, 0ull); dstride.assign(c->nsend ? c->nsend : 1, 0ull);
-        for (int p = 0; p < P; ++p)
-            for (int j = 0; j < c->scnt[p]; ++j) {
-                const size_t i = (size_t)c->sdsp[p] + j;
-                dst0[i] = (unsigned long long)(uintptr_t)rings[p] + 16ull * ((unsigned long long)theirs[2 * p] + j);
-                dstride[i] = 16ull * (unsigned long long)theirs[2 * p + 1];
-            }
-        c->push_dst0 = dev_upload(dst0.data(), dst0.size());
-        c->push_stride = dev_upload(dstride.data(), dstride.size());
-        c->ll_fused = c->n_bnd == 0 && c->ng_int + c->ng_bnd > 0;
-        // Ragged rows (jagged slices): the launch with the exchange inside runs k_spmv_sell's loop over EVERY group, the rank's
-        // halo-free groups included; as separate launches -- push, interior, unpack, boundary -- the interior goes through the
-        // three-trip products of bicg_jagw.hip. Worth two more launches when the interior is large (measured with two 800 k-row
-        // ranks of the RCM-numbered mesh matrix sharing a GPU: profiles/r06/ragged_ranks_fused_or_split.txt); BICG_PLAN="halo-fused=0|1" decides.
-        if (c->ll_fused && c->sell_jag && c->lane_info && c->jagw_fast && (uint64_t)c->nnz_d >= 4000000ull) c->ll_fused = false;
-        if (const char *sv = plan_tok("halo-fused")) c->ll_fused = c->n_bnd == 0 && c->ng_int + c->ng_bnd > 0 && atoi(sv) != 0;
-        if (const char *sv = knob_x("BICG_P2P_FUSED")) c->ll_fused = c->ll_fused && atoi(sv) != 0;
-        if (c->ll_fused) {
-            std::vector<uint32_t> order(gl_int);
-            order.insert(order.end(), gl_bnd.begin(), gl_bnd.end());
-            c->glist_ll = dev_upload(order.data(), order.size());
-        }
-    } else {
-        c->p2p = nullptr;
-    }
-
-    ctx_state(c, comm, ngroups);
-    if (const char *sv = test_tok("spin-ticks")) c->spin_ticks = strtoull(sv, nullptr, 10);
-    // Round 4: with the products alternating direction and reading no column index in uniform slices, a big block is faster
-    // as two plain products + two element-wise kernels (Transport-shaped, one GPU: 139.0 vs 152.0 us per pipelined iteration;
-    // profiles/NOTES.md): the fused two-launch form stays what it was built for -- the latency-bound ranks.
-    c->fuse_pipe = c->fuse_small;
-    if (const char *sv = plan_tok("fuse-pipe")) c->fuse_pipe = atoi(sv) != 0;
-    else if (const char *pv = plan_tok("pipe-probe")) c->pipe_probe = atoi(pv);
-    c->spmm_ok = all_ranks(comm, spmm_possible(c));
-    c->fuse_plan_ok = all_ranks(comm, c->glist_all && c->nblk == 0 && (c->single() || (c->p2p && c->ll_fused)));
-    BICG_HIP(hipHostMalloc((void **)&c->hS, sizeof(Scal), hipHostMallocDefault));
-    memset(c->hS, 0, sizeof(Scal));
-    {   // persistent pipelined iteration for latency-bound ranks: available when the plan fits on EVERY rank
-        const bool off = knob_tok("BICG_PERSIST", "0") || knob_tok("BICG_PERSIST", "off");
-        bool mine = !off && persist_build(c, diag, optr, ocol, oval, send_idx, dst0, dstride);
-        c->persist_on = all_ranks(comm, mine);
-        if (const char *pp = knob_x("BICG_PERSIST_PLAIN")) c->persist_plain = atoi(pp) != 0;
-        if (!c->persist_on && mine) { for (void *p : c->persist_mem) (void)hipFree(p); c->persist_mem.clear(); c->persist = PersistArgs{}; }
-    }
-
-    plan_mark("transport, persistent plan");
-    ctx_streams(c, P);
-    plan_mark("streams");
-    preload_for(c);
-    plan_mark("code objects");
+    p2p_transport(c, comm, plan, halo);
+    ctx_finish(c, comm, plan.ngroups, diag, &halo, trace);
     return c;
 }
 
@@ -1429,10 +834,7 @@ bicg_ctx *bicg_create_device_csr(const double *val_d, const unsigned int *col_d,
     c->comm = comm; c->device = comm->device; c->nranks = 1; c->rank = 0;
     g_live.push_back(c);
     c->n_loc = rows; c->n_glob = rows; c->nnz_d = nnz;
-    if (const char *sv = knob_x("BICG_SELL_NT")) c->sell_nt_env = atoi(sv);
-    if (const char *sv = knob_x("BICG_SELL_ALT")) c->sell_alt = atoi(sv);
-    if (const char *sv = knob_x("BICG_SELL_XCD")) c->sell_xcd = atoi(sv);
-    if (const char *sv = test_tok("force-comm")) c->force_comm = atoi(sv) != 0;
+    ctx_read_switches(c);
     if (c->force_comm) die("bicg_create_device_csr", "BICG_TEST=force-comm is not supported on this path");
     c->overlap = nnz >= 6000000u; c->fuse_small = nnz < 6000000u;
     c->scnt.assign(1, 0); c->sdsp.assign(1, 0); c->rcnt.assign(1, 0); c->rdsp.assign(1, 0);
@@ -1593,7 +995,7 @@ bicg_ctx *bicg_create_device_csr(const double *val_d, const unsigned int *col_d,
                 BICG_HIP(hipMemcpy(c->s_ubase, ubase.data(), sizeof(uint32_t) * nslices, hipMemcpyHostToDevice));
                 if (c->s_vbase) BICG_HIP(hipMemcpy(c->s_vbase, vbase.data(), sizeof(uint32_t) * nslices, hipMemcpyHostToDevice));
                 if (c->s_mbase) BICG_HIP(hipMemcpy(c->s_mbase, mbase.data(), sizeof(uint32_t) * nslices, hipMemcpyHostToDevice));
-                if (getenv("BICG_PLAN_TRACE")) fprintf(stderr, "bicgstab_hip: %u list-driven slices did not match their list (hash collision): stored as general slices\n", nbad);
+                if (plan_trace_env()) fprintf(stderr, "bicgstab_hip: %u list-driven slices did not match their list (hash collision): stored as general slices\n", nbad);
             }
         }
         if (constant_entries) build_slice_desc(c, nslices, rows, slen.data(), ubase, vbase, mbase, uoff, uval, nullptr);
@@ -1617,17 +1019,8 @@ bicg_ctx *bicg_create_device_csr(const double *val_d, const unsigned int *col_d,
     if (c->s_desc) c->matrix_bytes += 8ull * nslices;
     c->device_matrix_bytes = 8ull * ((uint64_t)rows + 1) + 8ull * entries + (c16 ? 2ull * n16 : 4ull * entries) + 12ull * nslices;
     BICG_HIP(hipFree(far_d));
-    ctx_state(c, comm, ngroups);
-    if (const char *sv = test_tok("spin-ticks")) c->spin_ticks = strtoull(sv, nullptr, 10);
-    c->fuse_pipe = c->fuse_small;
-    if (const char *sv = plan_tok("fuse-pipe")) c->fuse_pipe = atoi(sv) != 0;
-    else if (const char *pv = plan_tok("pipe-probe")) c->pipe_probe = atoi(pv);
-    c->spmm_ok = spmm_possible(c);
-    c->fuse_plan_ok = true;
-    BICG_HIP(hipHostMalloc((void **)&c->hS, sizeof(Scal), hipHostMallocDefault));
-    memset(c->hS, 0, sizeof(Scal));
-    ctx_streams(c, 1);
-    preload_for(c);
+    PlanTrace quiet;
+    ctx_finish(c, comm, ngroups, nullptr, nullptr, quiet);
     if (plan_seconds) *plan_seconds = now_sec() - t0;
     return c;
 }

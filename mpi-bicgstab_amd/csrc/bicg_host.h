@@ -2,7 +2,8 @@
 // device-memory helpers, section timing, and the prototypes of the functions that cross file boundaries.
 //   bicg_solver.cpp   dot groups, the distributed SpMV, the four iterations of reference src/solver.c, run_begin / iterate / end
 //   bicg_shifted.cpp  the shifted family (src/shifted_solver.c, src/shifted_switching_solver.c) and its section prints
-//   bicg_create.cpp   the plan: bicg_create / bicg_create_device_csr, slice descriptors, stencil plan, persistent set-up, destroy
+//   bicg_create.cpp   bicg_create / bicg_create_device_csr: halo plan, upload of the diag block's plan (made by bicg_sell_plan.cpp,
+//                     host only: bicg_plan.h), slice descriptors, stencil plan, transport, persistent set-up, destroy
 //   bicg_dropin.cpp   the reference's own symbols (solver.h, shifted_solver.h, shifted_switching_solver.h), matrix residency
 //   bicg_api.cpp      the additive handle API (load / fetch / spmv / dot / spmm / info calls)
 #pragma once
@@ -381,9 +382,10 @@ int run_shifted(bicg_ctx *c, int mode, double *x_set_host, double *r_host, const
 // ---- plan and context (bicg_create.cpp)
 bool all_ranks(Comm *comm, bool mine);
 void sell_order_for_big_grids(bicg_ctx *c, uint32_t ngroups);
+// ---- persistent launches (bicg_solver.cpp; the shifted family's: bicg_shifted.cpp)
 bool persist_chunk(bicg_ctx *c, int niter);
-bool persist_chunk_shifted(bicg_ctx *c, int mode, int niter, int it0, int nsig, int seed, double shift);
 void persist_account(bicg_ctx *c);
+bool persist_chunk_shifted(bicg_ctx *c, int mode, int niter, int it0, int nsig, int seed, double shift);
 // ---- drop-in entry points (bicg_dropin.cpp)
 void check_square(const INFO_Matrix *info);
 void env_options(bicg_options *o);

@@ -101,4 +101,34 @@ inline const char *knob_x(const char *) { return nullptr; }
 constexpr bool kExperiments = false;
 #endif
 
+// Every switch the sliced-ELL plan of the diag block consults (sell_plan_host, bicg_sell_plan.cpp), read once by
+// read_plan_switches(); the plan itself never looks at the environment. -1 = the token is absent (the plan decides).
+struct PlanSwitches {
+    int layout = -1;             // BICG_PLAN="layout=pad|jag": 0 padded, 1 jagged (any other text: absent)
+    int window = -1;             // BICG_PLAN="window=0|1": never / whenever it fits
+    bool window_list = true;     // BICG_PLAN="window-list=0" keeps the gathers
+    bool col16 = true;           // BICG_PLAN="col16=0": 32-bit columns
+    bool uniform = true, constant = true, masked = true;      // BICG_PLAN="uniform=0" / "constant=0" / "masked=0"
+    int jagw = -1;               // BICG_PLAN="jagw=0|1": k_spmv_sell's loop / the three-trip products
+    bool no_sell = false;        // BICG_NO_SELL=1 (experiments): every row to the CSR kernels
+    int rowsplit = -1;           // BICG_ROWSPLIT=0|1 (experiments): rows over lanes never / always
+    bool sell_sort = true;       // BICG_SELL_SORT=0 (experiments): windows without dealing the rows by length
+};
+inline PlanSwitches read_plan_switches()
+{
+    PlanSwitches s;
+    if (const char *sv = plan_tok("layout")) s.layout = !strcmp(sv, "jag") ? 1 : !strcmp(sv, "pad") ? 0 : -1;
+    if (const char *sv = plan_tok("window")) s.window = atoi(sv);
+    s.window_list = !plan_off("window-list");
+    s.col16 = !plan_off("col16");
+    s.uniform = !plan_off("uniform");
+    s.constant = !plan_off("constant");
+    s.masked = !plan_off("masked");
+    if (const char *sv = plan_tok("jagw")) s.jagw = atoi(sv) != 0;
+    s.no_sell = knob_x("BICG_NO_SELL") && atoi(knob_x("BICG_NO_SELL"));
+    if (const char *sv = knob_x("BICG_ROWSPLIT")) s.rowsplit = atoi(sv) != 0;
+    s.sell_sort = !(knob_x("BICG_SELL_SORT") && atoi(knob_x("BICG_SELL_SORT")) == 0);
+    return s;
+}
+
 }  // namespace bicg

@@ -4,6 +4,8 @@
 //   bicg_halo_plan   which entries of x an offd block really needs  (replaces the full-vector
 //                    MPI_Iallgatherv of reference src/matrix.c:432 by a halo)
 //   bicg_row_blocks  greedy row blocks for the row-block-stream SpMV
+//   bicg_persist_plan / bicg_sell_plan_digest   C views for tests of the two host-only plans (persist_plan_host below;
+//                    sell_plan_host, bicg_sell_plan.cpp)
 #include "../../include/bicgstab_hip.h"
 #include "bicg_plan.h"
 #include "bicg_parallel.h"
@@ -311,5 +313,23 @@ extern "C" int bicg_persist_plan(const CSR_Matrix *diag, const CSR_Matrix *offd_
     if (rdiag) std::copy(P.rdiag.begin(), P.rdiag.end(), rdiag);
     if (win_ptr) std::copy(P.wptr.begin(), P.wptr.end(), win_ptr);
     if (win_runs) std::copy(P.runs.begin(), P.runs.end(), win_runs);
+    return 0;
+}
+
+// C view for tests of the sliced-ELL plan (sell_plan_host, bicg_sell_plan.cpp) with the switches of the environment: what
+// bicg_create would plan for this diag block as rank of `nranks`, as a summary and one FNV-1a digest per array (orders:
+// include/bicgstab_hip.h section 5). offd_renumbered: its row pointers say which rows touch the halo; NULL for one rank.
+extern "C" int bicg_sell_plan_digest(const CSR_Matrix *diag, const CSR_Matrix *offd_renumbered, int nranks, unsigned int rows_global,
+                                     unsigned long long nnz_diag_global, unsigned long long summary[22], unsigned long long digest[26])
+{
+    static_assert(bicg::kSellSummaryLen == 22 && bicg::kSellDigestLen == 26, "lengths documented in bicgstab_hip.h");
+    if (!diag || nranks < 1 || (nranks > 1 && !offd_renumbered)) return 1;
+    bicg::PlanFacts facts;
+    facts.P = nranks; facts.rows_global = rows_global; facts.nnz_diag_all = nnz_diag_global;
+    facts.fuse_small = nnz_diag_global / (unsigned long long)nranks < 6000000u;
+    bicg::SellPlan plan;
+    if (!bicg::sell_plan_host(diag, offd_renumbered ? offd_renumbered->ptr : nullptr, facts, bicg::read_plan_switches(), plan)) return 1;
+    bicg::sell_plan_summary(plan, summary);
+    bicg::sell_plan_digest(plan, digest);
     return 0;
 }

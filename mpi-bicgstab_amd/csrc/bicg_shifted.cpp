@@ -232,6 +232,50 @@ int run_switching(bicg_ctx *c, int mode, double *x_set_host, double *r_host, con
     return k_ref;
 }
 
+// niter iterations of shifted_pipe_lopbicgstab (reference src/shifted_solver.c:794-866) in one launch: the seed system's
+// pipelined recurrence with products of A + sigma_seed I, every other shift's p_j / x_j streamed through in phase 2. Sequence
+// numbers as for the pipelined kernel (dense, reported back: persist_account).
+bool persist_chunk_shifted(bicg_ctx *c, int mode, int niter, int it0, int nsig, int seed, double shift)
+{
+    const bool pipe = mode == SH_PIPE;          // else shifted_lopbicgstab: three groups and two products per iteration, numbered
+                                                // like the plain kernel's (fixed counts, advanced here)
+    if (c->grp.active) die("internal", "persistent chunk with an open dot group");
+    const size_t st = c->stride;
+    PersistArgs a = c->persist;
+    a.v = c->v;
+    a.v.x = c->x_set + (size_t)seed * st; a.v.p = c->p_set + (size_t)seed * st;      // x[seed], p[seed]
+    a.S = c->S; a.alarm = c->alarm; a.niter = niter;
+    a.seq0 = c->persist_seq; a.vseq0 = c->persist_vseq;
+    a.it0 = it0; a.krr = 0; a.nrr = 0; a.force_first = 0; a.drift_every = 0; a.drift_tol2 = 0.0;
+    a.pset = c->p_set; a.xset = c->x_set; a.set_stride = (uint32_t)st; a.nsig = nsig; a.seed = seed;
+    a.shift = shift; a.has_shift = 1;
+    {   // the sets stay in the Infinity Cache when they (and the matrix, if it is not in LDS) fit half of it
+        const double ws = 16.0 * (double)nsig * (double)st + (a.mat_entries ? 0.0 : (double)c->matrix_bytes);
+        a.set_nt = ws > 0.5 * 256.0 * 1048576.0;
+        if (const char *e = knob_x("BICG_SHP_NT")) a.set_nt = atoi(e) != 0;
+    }
+    a.timeout_ticks = c->p2p ? c->p2p->timeout_ticks : 200000000ull;
+    static const int xcd_map = knob_x("BICG_PERSIST_XCD") ? atoi(knob_x("BICG_PERSIST_XCD")) : 1;
+    a.xcd_map = xcd_map;
+    static const int first_sleep = knob_x("BICG_PERSIST_SLEEP") ? atoi(knob_x("BICG_PERSIST_SLEEP")) : 1;
+    a.first_sleep = (unsigned)first_sleep;
+    if (!pipe) c->persist_seq += 3u * (unsigned)niter;
+    if (a.multi) {
+        a.halo_seq0 = c->halo_seq;
+        a.p2p = c->p2p->red_desc(c->p2p->red_seq);
+        if (!pipe) { c->halo_seq += 2u * (unsigned)niter; c->p2p->red_seq += 3u * (unsigned)niter; }
+        a.ring = c->halo_ring;
+        c->halo_unsynced = 0;
+    }
+    const hipError_t err = pipe ? launch_shpipe_persist(a, c->sc) : launch_shlop_persist(a, c->sc);
+    if (err != hipSuccess) {
+        if (c->nranks > 1) die("persistent kernel", "launch failed on a multi-rank run (BICG_PERSIST=0 selects the multi-launch iteration)");
+        fprintf(stderr, "bicgstab_hip: falling back to the multi-launch iteration\n");
+        return false;
+    }
+    return true;
+}
+
 int run_shifted(bicg_ctx *c, int mode, double *x_set_host, double *r_host, const double *sigma, int nsig, int seed,
                 const bicg_options *opt_in, bicg_result *res)
 {

@@ -875,6 +875,96 @@ bool graph_iteration(bicg_ctx *c, Driver &d)
     return true;
 }
 
+// niter iterations of pipe_bicgstab in one launch (the open dot group has been closed: fetch_scal precedes every chunk)
+bool persist_chunk(bicg_ctx *c, int niter)
+{
+    if (c->grp.active) die("internal", "persistent chunk with an open dot group");
+    if (c->f1_done) die("internal", "persistent chunk after phase 1 of the next iteration has run");
+    const bool plain = c->method == BICG_BICGSTAB;
+    const bool pipe = c->method >= BICG_PIPE_BICGSTAB;
+    const unsigned groups = plain ? 3u : 2u;                  // dot groups (tags, mailbox numbers) per iteration
+    PersistArgs a = c->persist;
+    a.v = c->v; a.S = c->S; a.alarm = c->alarm; a.niter = niter;
+    a.seq0 = c->persist_seq;
+    a.vseq0 = c->persist_vseq;
+    // the pipelined kernel numbers hand-offs and groups densely and reports what it used (replacement iterations and drift
+    // checks make the count data dependent): persist_account() advances the counters after the launch
+    if (!pipe) c->persist_seq += groups * (unsigned)niter;
+    a.it0 = c->it;
+    a.krr = c->method == BICG_PIPE_BICGSTAB_RR ? c->opt.krr : 0; a.nrr = c->opt.nrr;
+    a.force_first = 0;
+    a.drift_every = (pipe && c->opt.rr_drift > 0.0) ? c->opt.check_every : 0;
+    a.drift_tol2 = c->opt.rr_drift * c->opt.rr_drift;
+    a.timeout_ticks = c->p2p ? c->p2p->timeout_ticks : 200000000ull;          // 2 s inside one GPU
+    static const int xcd_map = knob_x("BICG_PERSIST_XCD") ? atoi(knob_x("BICG_PERSIST_XCD")) : 1;
+    a.xcd_map = xcd_map;
+    static const int first_sleep = knob_x("BICG_PERSIST_SLEEP") ? atoi(knob_x("BICG_PERSIST_SLEEP")) : 1;
+    a.first_sleep = (unsigned)first_sleep;
+    if (a.multi) {
+        // every rank advances its exchange and group numbers by the whole chunk, converged early or not
+        a.halo_seq0 = c->halo_seq;
+        a.p2p = c->p2p->red_desc(c->p2p->red_seq);
+        if (!pipe) { c->halo_seq += 2u * (unsigned)niter; c->p2p->red_seq += groups * (unsigned)niter; }
+        a.ring = c->halo_ring;
+        c->halo_unsynced = 0;
+    }
+    if (a.multi) {
+        if (!c->waitlog) { c->waitlog = dev_alloc<unsigned>(3 * (size_t)kWaitCap); BICG_HIP(hipMemsetAsync(c->waitlog, 0, sizeof(unsigned) * 3 * kWaitCap, c->sc)); }
+        a.waitlog = c->waitlog; a.waitcap = kWaitCap;
+    }
+    static const bool want_trace = knob_x("BICG_PERSIST_TRACE") != nullptr;
+    unsigned long long *dbg = nullptr;
+    if (want_trace) {
+        dbg = dev_alloc<unsigned long long>(64 * 16);
+        BICG_HIP(hipMemset(dbg, 0, 64 * 16 * sizeof(unsigned long long)));
+        a.dbg = dbg;
+    }
+    hipError_t err;
+    if (plain) err = launch_plain_persist(a, c->sc);
+    else if (c->method == BICG_CA_BICGSTAB) err = launch_ca_persist(a, c->sc);
+    else err = launch_pipe_persist(a, c->sc);
+    if (err != hipSuccess) {
+        // nothing ran: hand the chunk back to the multi-launch kernels (every rank sees the same failure: same kernel, same
+        // plan limits; the sequence numbers reserved above are simply skipped on all of them)
+        if (dbg) (void)hipFree(dbg);
+        if (c->nranks > 1) die("persistent kernel", "launch failed on a multi-rank run (BICG_PERSIST=0 selects the multi-launch iteration)");
+        fprintf(stderr, "bicgstab_hip: falling back to the multi-launch iteration\n");
+        c->persist_on = false;
+        return false;
+    }
+    if (want_trace && c->method != BICG_PIPE_BICGSTAB) { BICG_HIP(hipStreamSynchronize(c->sc)); BICG_HIP(hipFree(dbg)); }
+    if (want_trace && c->method == BICG_PIPE_BICGSTAB) {
+        // 10 ns ticks of one row workgroup (0 start, 1 z and partials published, 2 window staged, 3 product done, 4 omega here,
+        // 5 w and partials published, 6 window, 7 product, 8 scalars here) and of the helper (10 / 11: group 1 / 2 published)
+        std::vector<unsigned long long> h(64 * 16);
+        BICG_HIP(hipStreamSynchronize(c->sc));
+        BICG_HIP(hipMemcpy(h.data(), dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        BICG_HIP(hipFree(dbg));
+        for (int it = std::max(0, std::min(niter, 32) - 5); it < std::min(niter, 32); ++it)
+            for (int who = 0; who < 2; ++who) {
+                const unsigned long long *q = h.data() + (size_t)(it * 2 + who) * 16, *q0 = h.data() + (size_t)(it * 2) * 16;
+                fprintf(stderr, "persist trace it %2d %s:", it, who ? "comm" : "row ");
+                for (int i = 0; i <= 8; ++i) fprintf(stderr, " %d:%+.2f", i, 0.01 * (double)(long long)(q[i] - q0[0]));
+                if (!who) fprintf(stderr, "  helper g1 %+.2f g2 %+.2f", 0.01 * (double)(long long)(q[10] - q0[0]), 0.01 * (double)(long long)(q[11] - q0[0]));
+                else fprintf(stderr, "  helper g1: arrived %+.2f summed %+.2f applied %+.2f", 0.01 * (double)(long long)(q[12] - q0[0]),
+                             0.01 * (double)(long long)(q[13] - q0[0]), 0.01 * (double)(long long)(q[14] - q0[0]));
+                fprintf(stderr, "\n");
+            }
+    }
+    return true;
+}
+
+// after a pipelined persistent launch (fetch_scal has brought the scalar block back): advance the sequence counters by what
+// the launch consumed. Identical on every rank -- the decisions inside the launch depend on globally reduced sums only.
+void persist_account(bicg_ctx *c)
+{
+    const unsigned nv = (unsigned)c->hS->red[kRedUsedV], ng = (unsigned)c->hS->red[kRedUsedG];
+    c->persist_seq += ng;
+    c->persist_vseq += nv;
+    if (!c->single()) { c->halo_seq += nv; c->p2p->red_seq += ng; }
+    c->adaptive_rr += (int)c->hS->red[kRedAdaptive];
+}
+
 int run_iterate(bicg_ctx *c, int nsteps)
 {
     const bicg_options &o = c->opt;

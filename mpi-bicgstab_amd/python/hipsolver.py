@@ -61,7 +61,7 @@ EXPORTS = [
     "bicg_comm_init_single", "bicg_comm_finalize", "bicg_comm_selftest_rccl", "bicg_comm_rccl_loadable", "bicg_comm_last_error", "bicg_section_times", "bicg_comm_rank", "bicg_comm_size",
     "bicg_default_options", "bicg_create", "bicg_destroy", "bicg_solve", "bicg_load", "bicg_run", "bicg_fetch",
     "bicg_run_begin", "bicg_run_iterate", "bicg_run_iterate_timed", "bicg_run_end", "bicg_sync", "bicg_trace", "bicg_spmv", "bicg_dot", "bicg_spmv_bench", "bicg_plan_info", "bicg_ctx_flags", "bicg_spmm", "bicg_device_matrix_bytes", "bicg_uniform_entries", "bicg_constant_entries", "bicg_masked_rows", "bicg_stencil_info", "bicg_stencil_rows_per_lane", "bicg_comm_wait_stats", "bicg_plan_collisions", "bicg_product_kernels", "bicg_spmv_matrix_bytes", "bicg_last_shifted_persistent", "bicg_last_spmm_windowed", "bicg_dropin_context", "bicg_dropin_release", "bicg_dropin_stats",
-    "bicg_mtx_load_block", "bicg_mtx_free", "bicg_partition", "bicg_halo_plan", "bicg_halo_send_counts", "bicg_halo_send_lists", "bicg_row_blocks", "bicg_window_plan", "bicg_window_slot", "bicg_version", "bicg_has_experiments", "bicg_switch_value", "bicg_switch_unknown", "bicg_stream_bench", "bicg_create_device_csr", "bicg_stencil7_device", "bicg_device_free", "bicg_persist_plan", "bicg_set_plan_threads",
+    "bicg_mtx_load_block", "bicg_mtx_free", "bicg_partition", "bicg_halo_plan", "bicg_halo_send_counts", "bicg_halo_send_lists", "bicg_row_blocks", "bicg_window_plan", "bicg_window_slot", "bicg_version", "bicg_has_experiments", "bicg_switch_value", "bicg_switch_unknown", "bicg_stream_bench", "bicg_create_device_csr", "bicg_stencil7_device", "bicg_device_free", "bicg_persist_plan", "bicg_set_plan_threads", "bicg_sell_plan_digest",
 ]
 
 _lib = None
@@ -545,6 +545,39 @@ def persist_plan(blocks: HostBlocks, nranks: int, gmax: int):
     assert rc2 == 0
     return dict(spw=spw, rpt=rpt, nwg=nwg, win_slots=win_slots, max_runs=max_runs, max_entries=max_entries, entries=entries, halo=halo,
                 pbase=pbase, pslot=pslot[:entries], pval=pval[:entries], rlen=rlen, rdiag=rdiag, wptr=wptr, runs=runs[:2 * nruns].reshape(-1, 2))
+
+
+# bicg_sell_plan_digest (include/bicgstab_hip.h section 5): names of the summary's entries and of the arrays behind the digests
+SELL_SUMMARY = ("jag", "c16", "clusters", "window", "retried", "rowsplit", "sell_entries", "sell_nnz", "sell_rows", "uniform_entries",
+                "constant_entries", "masked_rows", "nblk", "ng_int", "ng_bnd", "csr16", "win_slots", "win_max_runs", "win_near16",
+                "jag_tail16_max", "n_bnd", "lane_info")
+SELL_ARRAYS = ("slice_len", "slice_base", "slice_base16", "sval", "scol", "scol16", "perm", "group_is_sell", "gl_int", "gl_bnd", "bint",
+               "bbnd", "win_ptr", "win_runs", "list", "lptr", "total", "ubase", "vbase", "mbase", "uoff", "uval", "rmask", "lane_info",
+               "dcol16", "fw")
+
+
+def sell_plan_digest(blocks: HostBlocks, nranks: int = 1, rows_global: int | None = None, nnz_diag_global: int | None = None):
+    """The sliced-ELL plan bicg_create would make for this rank's diag block under the BICG_PLAN of the environment, without a
+    GPU: (summary dict keyed by SELL_SUMMARY, digest dict keyed by SELL_ARRAYS: 64-bit FNV-1a of each array of the plan).
+    rows_global / nnz_diag_global: rows and diag non-zeros of all ranks (default: this block's, i.e. one rank's)."""
+    L = lib()
+    _ullp = C.POINTER(C.c_ulonglong)
+    L.bicg_sell_plan_digest.argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.c_int, C.c_uint, C.c_ulonglong, _ullp, _ullp]
+    offd_p, keep = None, None
+    if nranks > 1:
+        halo, _, _, ren = halo_plan(blocks, nranks)
+        nz = int(blocks.offd.ptr[blocks.offd.rows])
+        ren = np.ascontiguousarray(ren[:max(nz, 1)], dtype=np.uint32)
+        keep = (ren,)
+        o = CSRMatrix(blocks.offd.val, ren.ctypes.data_as(_up), blocks.offd.ptr, nz, blocks.offd.rows, blocks.n_loc + halo)
+        offd_p = C.byref(o)
+    rows_global = int(blocks.info.rows) if rows_global is None else rows_global
+    nnz_diag_global = int(blocks.diag.ptr[blocks.diag.rows]) if nnz_diag_global is None else nnz_diag_global
+    summ, dig = (C.c_ulonglong * len(SELL_SUMMARY))(), (C.c_ulonglong * len(SELL_ARRAYS))()
+    if L.bicg_sell_plan_digest(C.byref(blocks.diag), offd_p, nranks, rows_global, nnz_diag_global, summ, dig) != 0:
+        raise RuntimeError("bicg_sell_plan_digest failed")
+    del keep
+    return dict(zip(SELL_SUMMARY, (int(v) for v in summ))), dict(zip(SELL_ARRAYS, (int(v) for v in dig)))
 
 
 def partition(n: int, nranks: int):
