@@ -338,8 +338,15 @@ enum { BICG_FLAG_P2P = 1, BICG_FLAG_LL_FUSED = 2, BICG_FLAG_OVERLAP = 4, BICG_FL
        BICG_FLAG_CONSTANT = 8192  /* ... and some of them are CONSTANT: entry k also holds the same value in all 64 rows (the interior
                                      of a constant-coefficient stencil such as the 7-point Laplacian of BASELINE.json configs[3]):
                                      the values come from a shared list too and the slice streams nothing from the matrix arrays;
-                                     bicg_constant_entries counts those entries. Same products, same order: bit-identical */ };
+                                     bicg_constant_entries counts those entries. Same products, same order: bit-identical */,
+       BICG_FLAG_REORDERED = 16384 /* BICG_PLAN="reorder=1|2": bicg_create renumbered the diag block (P A P^T, reverse Cuthill-McKee,
+                                     one rank only) before planning it; every vector the caller hands in or gets back crosses the
+                                     permutation on the device, so the caller keeps its own numbering. The entries of a row keep
+                                     their stored order: products stay bit-identical to mult() on the caller's matrix */ };
 unsigned int bicg_ctx_flags(bicg_ctx *ctx);
+/* The reordering of a context with BICG_FLAG_REORDERED: the stats of bicg_reorder_plan (section 5) with out[7] = microseconds
+ * bicg_create spent on ordering + permuting. Returns 0; 1 and zeros when the context is not reordered. */
+int bicg_reorder_info(bicg_ctx *ctx, unsigned long long out[8]);
 /* bytes of MATRIX storage this context keeps on the GPU (CSR and/or sliced-ELL arrays, row pointers, offd block) */
 unsigned long long bicg_device_matrix_bytes(bicg_ctx *ctx);
 /* sliced-ELL entries (padding included) whose column indices the SpMV does not read (BICG_FLAG_UNIFORM), and the bytes one
@@ -455,6 +462,19 @@ int bicg_persist_plan(const CSR_Matrix *diag, const CSR_Matrix *offd_renumbered,
  *   digest of no bytes). Returns 0 on success. */
 int bicg_sell_plan_digest(const CSR_Matrix *diag, const CSR_Matrix *offd_renumbered, int nranks, unsigned int rows_global,
                           unsigned long long nnz_diag_global, unsigned long long summary[22], unsigned long long digest[26]);
+
+/* Bandwidth-reducing renumbering of a diag block (host only, what bicg_create does under
+ * BICG_PLAN="reorder=1|2"). Reverse Cuthill-McKee on the symmetrised pattern (entry (i, j) makes i and j neighbours whichever of
+ * the two is stored; the diagonal is ignored): one breadth-first sweep per connected component from its lowest-numbered vertex of
+ * minimum degree, components in ascending order of that vertex, within a level by (parent's position, degree, original index),
+ * each component's order reversed; rows without neighbours last, in their original order. A pure function of the pattern.
+ * perm[new] = old for the diag block (rows entries, caller-allocated). method: 1 = RCM. stats = {0 rows, 1 connected components,
+ * 2 bandwidth max|i-j| as given, 3 after, 4 most distinct columns of a 256-row group as given, 5 after, 6 rows without
+ * neighbours, 7 0}. Returns 0. */
+int bicg_reorder_plan(const CSR_Matrix *diag, int method, unsigned int *perm, unsigned long long stats[8]);
+/* P A P^T with the stored entry order of every row kept; out arrays caller-allocated (rows + 1, nz, nz). Returns 0, -1 when
+ * perm is not a permutation of 0..rows-1. */
+int bicg_permute_block(const CSR_Matrix *diag, const unsigned int *perm, unsigned int *ptr_out, unsigned int *col_out, double *val_out);
 
 /* Matrix-Market block loader (host only): what MPI_csr_load_matrix_block produces for `rank` of
  * `nranks` (reference src/matrix.c:402-419) -- diag block with local columns, offd block with global

@@ -2,14 +2,52 @@
 // shifted residuals / information calls. Split from bicg_solver.cpp in round 5; see bicg_host.h.
 #include "bicg_host.h"
 
+// ---- a reordered context's host copies (vec_upload / vec_download, bicg_host.h): through the staging buffer and the permutation
+// kernels, everything on the compute stream in order with what follows; sets larger than the buffer go in chunks
+static void reorder_stage(bicg_ctx *c, int nvec)
+{
+    const int want = std::min(nvec, kSpmmCols);
+    if (c->ro_stage_vecs >= want) return;
+    if (c->ro_stage) { BICG_HIP(hipStreamSynchronize(c->sc)); BICG_HIP(hipFree(c->ro_stage)); }
+    c->ro_stage = dev_alloc<double>((size_t)want * c->stride);
+    c->ro_stage_vecs = want;
+}
+void reorder_upload(bicg_ctx *c, double *dev, size_t dev_stride, const double *host, int nvec, bool async)
+{
+    const size_t n = c->n_loc;
+    reorder_stage(c, nvec);
+    // (the blocking form stands where a hipMemcpy stood: what the caller put on the null stream before it -- memsets of the
+    // destination -- is done before the kernel writes, and the vector is there when the call returns)
+    if (!async) BICG_HIP(hipDeviceSynchronize());
+    for (int j0 = 0; j0 < nvec; j0 += c->ro_stage_vecs) {
+        const int nv = std::min(c->ro_stage_vecs, nvec - j0);
+        for (int j = 0; j < nv; ++j)
+            BICG_HIP(hipMemcpyAsync(c->ro_stage + (size_t)j * c->stride, host + (size_t)(j0 + j) * n, sizeof(double) * n, hipMemcpyHostToDevice, c->sc));
+        launch_permute_in(c->ro_stage, c->stride, dev + (size_t)j0 * dev_stride, dev_stride, c->ro_perm, c->n_loc, nv, c->sc);
+    }
+    if (!async) BICG_HIP(hipStreamSynchronize(c->sc));
+}
+void reorder_download(bicg_ctx *c, double *host, const double *dev, size_t dev_stride, int nvec, bool async)
+{
+    const size_t n = c->n_loc;
+    reorder_stage(c, nvec);
+    for (int j0 = 0; j0 < nvec; j0 += c->ro_stage_vecs) {
+        const int nv = std::min(c->ro_stage_vecs, nvec - j0);
+        launch_permute_out(dev + (size_t)j0 * dev_stride, dev_stride, c->ro_stage, c->stride, c->ro_inv, c->n_loc, nv, c->sc);
+        for (int j = 0; j < nv; ++j)
+            BICG_HIP(hipMemcpyAsync(host + (size_t)(j0 + j) * n, c->ro_stage + (size_t)j * c->stride, sizeof(double) * n, hipMemcpyDeviceToHost, c->sc));
+    }
+    if (!async) BICG_HIP(hipStreamSynchronize(c->sc));
+}
+
 extern "C" {
 
 int bicg_load(bicg_ctx *c, const double *x0, const double *b)
 {
     use_device(c);
     x0 = host_in(c, x0); b = host_in(c, b);
-    BICG_HIP(hipMemcpy(c->v.x, x0, sizeof(double) * c->n_loc, hipMemcpyHostToDevice));
-    BICG_HIP(hipMemcpy(c->v.r, b, sizeof(double) * c->n_loc, hipMemcpyHostToDevice));
+    vec_upload(c, c->v.x, c->stride, x0);
+    vec_upload(c, c->v.r, c->stride, b);
     return 0;
 }
 
@@ -18,8 +56,8 @@ int bicg_fetch(bicg_ctx *c, double *x, double *r)
     use_device(c);
     BICG_HIP(hipStreamSynchronize(c->sc));
     x = host_out(c, x); r = host_out(c, r);
-    if (x) BICG_HIP(hipMemcpy(x, c->v.x, sizeof(double) * c->n_loc, hipMemcpyDeviceToHost));
-    if (r) BICG_HIP(hipMemcpy(r, c->v.r, sizeof(double) * c->n_loc, hipMemcpyDeviceToHost));
+    if (x) vec_download(c, x, c->v.x, c->stride);
+    if (r) vec_download(c, r, c->v.r, c->stride);
     return 0;
 }
 
@@ -75,10 +113,10 @@ int bicg_spmv(bicg_ctx *c, const double *x, double *y)
     use_device(c);
     reset_scal(c);
     x = host_in(c, x); y = host_out(c, y);
-    BICG_HIP(hipMemcpyAsync(c->v.p, x, sizeof(double) * c->n_loc, hipMemcpyHostToDevice, c->sc));
+    vec_upload(c, c->v.p, c->stride, x, 1, true);
     c->time_kernels = false;
     spmv(c, c->v.p, c->v.s, 0, nullptr, c->red(0, PH_NONE));
-    BICG_HIP(hipMemcpyAsync(y, c->v.s, sizeof(double) * c->n_loc, hipMemcpyDeviceToHost, c->sc));
+    vec_download(c, y, c->v.s, c->stride, 1, true);
     if (c->p2p) fetch_scal(c);      // also reports a peer that never delivered its halo values
     else BICG_HIP(hipStreamSynchronize(c->sc));
     return 0;
@@ -89,8 +127,8 @@ double bicg_dot(bicg_ctx *c, const double *x, const double *y)
     use_device(c);
     reset_scal(c);
     if (c->phantom) { x = host_in(c, x); y = x; }
-    BICG_HIP(hipMemcpyAsync(c->v.p, x, sizeof(double) * c->n_loc, hipMemcpyHostToDevice, c->sc));
-    BICG_HIP(hipMemcpyAsync(c->v.s, y, sizeof(double) * c->n_loc, hipMemcpyHostToDevice, c->sc));
+    vec_upload(c, c->v.p, c->stride, x, 1, true);
+    vec_upload(c, c->v.s, c->stride, y, 1, true);
     launch_dot(c->v.p, c->v.s, c->n_loc, c->S, c->red(0, PH_NONE, true, 1), c->sc);
     group_now(c, 1, PH_NONE);
     fetch_scal(c);
@@ -107,7 +145,7 @@ int bicg_shifted_residuals(bicg_ctx *c, const double *x_loc_set, const double *b
     reset_scal(c);
     x_loc_set = host_in(c, x_loc_set, (size_t)nsig); if (c->phantom) b_loc = x_loc_set;
     const size_t n = c->n_loc;
-    BICG_HIP(hipMemcpyAsync(c->v.b, b_loc, sizeof(double) * n, hipMemcpyHostToDevice, c->sc));
+    vec_upload(c, c->v.b, c->stride, b_loc, 1, true);
     BICG_HIP(hipMemsetAsync(c->v.t, 0, sizeof(double) * c->stride, c->sc));
     c->time_kernels = false;
     launch_dot(c->v.b, c->v.b, c->n_loc, c->S, c->red(0, PH_NONE, true, 1), c->sc);
@@ -121,9 +159,7 @@ int bicg_shifted_residuals(bicg_ctx *c, const double *x_loc_set, const double *b
         std::vector<double> sq(kSpmmCols);
         for (int j0 = 0; j0 < nsig; j0 += kSpmmCols) {
             const int nv = std::min(kSpmmCols, nsig - j0);
-            for (int j = 0; j < nv; ++j)
-                BICG_HIP(hipMemcpyAsync(c->mm_in + (size_t)j * c->stride, x_loc_set + (size_t)(j0 + j) * n, sizeof(double) * n,
-                                        hipMemcpyHostToDevice, c->sc));
+            vec_upload(c, c->mm_in, c->stride, x_loc_set + (size_t)j0 * n, nv, true);
             spmm_pass(c, nv, sigma + j0, true);
             BICG_HIP(hipMemcpyAsync(sq.data(), c->mm_out, sizeof(double) * kSpmmCols, hipMemcpyDeviceToHost, c->sc));
             fetch_scal(c);                                   // synchronises; reports a lost peer
@@ -142,7 +178,7 @@ int bicg_shifted_residuals(bicg_ctx *c, const double *x_loc_set, const double *b
     Vecs w = c->v;
     w.r = c->v.t;                               // zero vector: FDrift then yields || b - A x ||^2
     for (int j = 0; j < nsig; ++j) {
-        BICG_HIP(hipMemcpyAsync(c->v.p, x_loc_set + (size_t)j * n, sizeof(double) * n, hipMemcpyHostToDevice, c->sc));
+        vec_upload(c, c->v.p, c->stride, x_loc_set + (size_t)j * n, 1, true);
         c->cur_shift = sigma[j]; c->cur_has_shift = true;
         spmv(c, c->v.p, c->v.ax, 0, nullptr, c->red(0, PH_NONE));
         c->cur_has_shift = false; c->cur_shift = 0.0;
@@ -171,18 +207,14 @@ int bicg_spmm(bicg_ctx *c, const double *x_loc_set, const double *sigma, int nve
     float total = 0.f;
     for (int j0 = 0; j0 < nvec; j0 += kSpmmCols) {
         const int nv = std::min(kSpmmCols, nvec - j0);
-        for (int j = 0; j < nv; ++j)
-            BICG_HIP(hipMemcpyAsync(c->mm_in + (size_t)j * c->stride, x_loc_set + (size_t)(j0 + j) * n, sizeof(double) * n,
-                                    hipMemcpyHostToDevice, c->sc));
+        vec_upload(c, c->mm_in, c->stride, x_loc_set + (size_t)j0 * n, nv, true);
         if (sigma) spmm_stage_sigma(c, nv, sigma + j0);
         // the events ride on the kernel's launch (stamped at its start and end, what rocprofv3 reports): events recorded around the
         // launch count the dispatch from an idle queue behind the copies as kernel time (181-184 us against 155)
         spmm_pass(c, nv, sigma ? sigma + j0 : nullptr, false, true, e0, e1);
         if (!c->mm_win) launch_vectors_from_rows(c->mm_yt, c->stride, nv, c->n_loc, c->mm_in, c->sc);     // result back to shift-major (reuses mm_in)
         const double *ysrc = c->mm_win ? c->mm_yt : c->mm_in;
-        for (int j = 0; j < nv; ++j)
-            BICG_HIP(hipMemcpyAsync(y_loc_set + (size_t)(j0 + j) * n, ysrc + (size_t)j * c->stride, sizeof(double) * n,
-                                    hipMemcpyDeviceToHost, c->sc));
+        vec_download(c, y_loc_set + (size_t)j0 * n, ysrc, c->stride, nv, true);
         fetch_scal(c);
         float ms = 0.f;
         BICG_HIP(hipEventElapsedTime(&ms, e0, e1));
@@ -277,6 +309,11 @@ int bicg_stencil_info(bicg_ctx *c, unsigned int out[8])
 }
 unsigned int bicg_stencil_rows_per_lane(bicg_ctx *c) { return stencil_product(c) ? (c->st.wide ? c->st.wide : 1u) : 0u; }
 unsigned int bicg_plan_collisions(bicg_ctx *c) { return c->plan_collisions; }
+int bicg_reorder_info(bicg_ctx *c, unsigned long long out[8])
+{
+    for (int i = 0; i < 8; ++i) out[i] = c->reordered ? c->ro_stats[i] : 0ull;
+    return c->reordered ? 0 : 1;
+}
 unsigned int bicg_product_kernels(int reset)
 {
     const unsigned m = g_product_kernels;
@@ -304,6 +341,7 @@ unsigned int bicg_ctx_flags(bicg_ctx *c)
     if (c->pipe_probed && (c->probe_ms[0] > 0.0 || c->probe_ms[1] > 0.0)) f |= BICG_FLAG_PIPE_PROBED;
     if (c->uniform_entries) f |= BICG_FLAG_UNIFORM;
     if (c->constant_entries) f |= BICG_FLAG_CONSTANT;
+    if (c->reordered) f |= BICG_FLAG_REORDERED;
     return f;
 }
 

@@ -467,6 +467,7 @@ static void ctx_read_switches(bicg_ctx *c)
     if (const char *sv = knob_x("BICG_SELL_ALT")) c->sell_alt = atoi(sv);
     if (const char *sv = knob_x("BICG_SELL_XCD")) c->sell_xcd = atoi(sv);
     if (const char *sv = test_tok("force-comm")) c->force_comm = atoi(sv) != 0;
+    if (const char *sv = plan_tok("reorder")) c->reorder_mode = atoi(sv);
 }
 
 // what the halo plan leaves on the host for the later stages (uploads, the persistent plan, the transport)
@@ -566,6 +567,56 @@ static void halo_plan(bicg_ctx *c, Comm *comm, const CSR_Matrix *offd, const INF
     if (got < 0) die("bicg_create", "halo request outside the owner's rows");
     c->nsend = (uint32_t)got;
     for (int p = 1; p < P; ++p) c->sdsp[p] = c->sdsp[p - 1] + c->scnt[p - 1];
+}
+
+// BICG_PLAN="reorder=1|2" (DESIGN.md section 4.14b): the diag block renumbered by reverse Cuthill-McKee (bicg_reorder.cpp) before it is
+// planned, so that the kernels see a matrix they are already good at. Returns the block to plan and upload: the permuted one,
+// kept in the context's host vectors until bicg_create returns, or `diag` itself where the reordering is declined or -- mode 2 --
+// not worth it. `plan` holds the plan of the returned block when *planned comes back true.
+//   mode 1  always reorder
+//   mode 2  plan the block as given first; reorder only when that plan is jagged and ends without an x window, and keep the
+//           reordered plan only if it gains a window or 16-bit column offsets (stencil, banded and generator-order inputs are never
+//           touched)
+// One rank only, a decision: with contiguous row blocks a badly numbered matrix on P ranks keeps (P - 1) / P of its entries in the
+// offd block, where renumbering the diag block changes nothing.
+static const CSR_Matrix *reorder_block(bicg_ctx *c, const CSR_Matrix *diag, const uint32_t *optr, const PlanFacts &facts, const PlanSwitches &sw,
+                                       CSR_Matrix &ro, SellPlan &plan, bool *planned, PlanTrace &trace)
+{
+    *planned = false;
+    if (c->reorder_mode != 1 && c->reorder_mode != 2) return diag;
+    if (c->nranks > 1 || c->phantom) {
+        if (c->rank == 0)
+            fprintf(stderr, "bicgstab_hip: BICG_PLAN reorder=%d not taken (%s)\n", c->reorder_mode,
+                    c->nranks > 1 ? "one rank only: across ranks most entries of a badly numbered matrix are in the offd blocks" : "a rank without rows");
+        return diag;
+    }
+    if (c->reorder_mode == 2) {
+        if (!sell_plan_host(diag, optr, facts, sw, plan, &trace)) die("bicg_create", "internal: sorted slices do not add up");
+        *planned = true;
+        if (!(plan.jag && !plan.win)) return diag;          // the given numbering is not the problem
+    }
+    const double t0 = now_sec();
+    const uint32_t n = diag->rows;
+    std::vector<uint32_t> perm(n), inv(n);
+    unsigned long long stats[8];
+    reorder_rcm(diag, perm.data(), stats);
+    c->ro_ptr.resize((size_t)n + 1); c->ro_col.resize(std::max<uint32_t>(c->nnz_d, 1u)); c->ro_val.resize(std::max<uint32_t>(c->nnz_d, 1u));
+    if (!permute_block(diag, perm.data(), c->ro_ptr.data(), c->ro_col.data(), c->ro_val.data(), inv.data())) die("bicg_create", "internal: the reordering is not a permutation");
+    stats[7] = (unsigned long long)(1.0e6 * (now_sec() - t0));
+    trace.mark("reorder");
+    ro = *diag;
+    ro.ptr = c->ro_ptr.data(); ro.col = c->ro_col.data(); ro.val = c->ro_val.data();
+    if (c->reorder_mode == 2) {
+        SellPlan again;
+        if (!sell_plan_host(&ro, optr, facts, sw, again, &trace)) die("bicg_create", "internal: sorted slices do not add up");
+        if (!(again.win || (again.c16 && !plan.c16))) return diag;      // nothing gained: the first plan stands
+        plan = std::move(again);
+    }
+    c->reordered = true;
+    memcpy(c->ro_stats, stats, sizeof stats);
+    c->ro_perm = dev_upload(perm.data(), perm.size());
+    c->ro_inv = dev_upload(inv.data(), inv.size());
+    return &ro;
 }
 
 // The only place that turns the plan of the diag block (sell_plan_host, bicg_sell_plan.cpp) into device memory, and the one
@@ -769,16 +820,20 @@ bicg_ctx *bicg_create(const CSR_Matrix *diag, const CSR_Matrix *offd, const INFO
     PlanTrace trace(tv && atoi(tv) != 0 && comm->rank == 0);
     trace.mark("state, halo plan");
 
-    // ---- the plan of the diag block, on the host, and its upload
+    // ---- the plan of the diag block (renumbered first where BICG_PLAN="reorder" asks for it), on the host, and its upload
     const PlanSwitches sw = read_plan_switches();
     SellPlan plan;
-    if (!sell_plan_host(diag, halo.optr.data(), facts, sw, plan, &trace)) die("bicg_create", "internal: sorted slices do not add up");
+    CSR_Matrix ro_blk;
+    bool planned = false;
+    diag = reorder_block(c, diag, halo.optr.data(), facts, sw, ro_blk, plan, &planned, trace);
+    if (!planned && !sell_plan_host(diag, halo.optr.data(), facts, sw, plan, &trace)) die("bicg_create", "internal: sorted slices do not add up");
     sell_plan_upload(c, diag, plan, sw, halo);
     if (c->nranks > 1) stencil_across_ranks(c, comm, plan.gl_bnd);
     trace.mark("upload");
 
     p2p_transport(c, comm, plan, halo);
     ctx_finish(c, comm, plan.ngroups, diag, &halo, trace);
+    std::vector<uint32_t>().swap(c->ro_ptr); std::vector<uint32_t>().swap(c->ro_col); std::vector<double>().swap(c->ro_val);
     return c;
 }
 
@@ -836,6 +891,7 @@ bicg_ctx *bicg_create_device_csr(const double *val_d, const unsigned int *col_d,
     c->n_loc = rows; c->n_glob = rows; c->nnz_d = nnz;
     ctx_read_switches(c);
     if (c->force_comm) die("bicg_create_device_csr", "BICG_TEST=force-comm is not supported on this path");
+    if (c->reorder_mode) fprintf(stderr, "bicgstab_hip: BICG_PLAN reorder=%d not taken (bicg_create_device_csr plans on the device; the host plan of bicg_create reorders)\n", c->reorder_mode);
     c->overlap = nnz >= 6000000u; c->fuse_small = nnz < 6000000u;
     c->scnt.assign(1, 0); c->sdsp.assign(1, 0); c->rcnt.assign(1, 0); c->rdsp.assign(1, 0);
     c->sell_entries = entries; c->sell_nnz = nnz; c->sell_rows = rows; c->sell_jag = false;
@@ -1054,7 +1110,7 @@ void bicg_destroy(bicg_ctx *c)
     (void)hipDeviceSynchronize();
     void *ptrs[] = {c->d_val, c->d_col, c->d_ptr, c->o_val, c->o_col, c->o_ptr, c->desc_int, c->desc_bnd, c->s_val, c->s_col, c->s_base, c->s_len, c->s_col16, c->s_base16, c->s_ubase, c->s_uoff, c->s_vbase, c->s_uval, c->s_mbase, c->s_rmask, c->s_desc, c->s_uoff8, c->st_code, c->st_tab, c->st_cmask, c->st_wbits, c->d_col16, c->win_ptr, c->win_runs, c->win_list, c->win_lptr, c->win_ltotal, c->sell_perm, c->lane_info, c->waitlog, c->sh_dev, c->sh_arrays, c->p_set, c->x_set, c->glist_int, c->glist_bnd,
                     c->send_idx, c->sendbuf, c->slab, c->partial, c->shard_tot, c->counter, c->Sbuf, c->trace, c->sw_buf,
-                    c->wpart[0], c->wpart[1], c->shard_ll, c->tail_tab, c->tail_shard, c->alarm, c->mm_in, c->mm_xt, c->mm_yt, c->mm_part, c->mm_out, c->mm_sigma};
+                    c->wpart[0], c->wpart[1], c->shard_ll, c->tail_tab, c->tail_shard, c->alarm, c->mm_in, c->mm_xt, c->mm_yt, c->mm_part, c->mm_out, c->mm_sigma, c->ro_perm, c->ro_inv, c->ro_stage};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (void *p : c->persist_mem) if (p) (void)hipFree(p);
     release_p2p(c);

@@ -542,6 +542,10 @@ void preload_persist_kernels();
 void launch_colsum(const double *partial, unsigned nwg, double *out, hipStream_t st);          // out[col] = sum_wg partial[wg][col]
 void launch_rows_from_vectors(const double *x, size_t stride, int nvec, uint32_t n, double *xt, hipStream_t st);
 void launch_vectors_from_rows(const double *yt, size_t stride, int nvec, uint32_t n, double *y, hipStream_t st);
+// a reordered context's vectors crossing the permutation (bicg_reorder.hip), nvec vectors in one launch:
+// in: dst[j][new] = src[j][perm[new]]; out: dst[j][old] = src[j][inv[old]] -- gathers with coalesced stores either way
+void launch_permute_in(const double *src, size_t src_stride, double *dst, size_t dst_stride, const uint32_t *perm, uint32_t n, int nvec, hipStream_t st);
+void launch_permute_out(const double *src, size_t src_stride, double *dst, size_t dst_stride, const uint32_t *inv, uint32_t n, int nvec, hipStream_t st);
 // SpMV + pipelined phase in the epilogue (epi 1: phase 2 after v = A z; epi 2: phase 1 after t = A w); a.fin is
 // applied at the epilogue, a.red receives the phase's dot partials
 bool launch_spmv_sell_epi(const SpmvArgs &a, int epi, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,

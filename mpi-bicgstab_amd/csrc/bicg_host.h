@@ -235,6 +235,17 @@ struct bicg_ctx {
     int  mm_win_env = 3;         // BICG_PLAN="spmm-window=0": the row-major kernel, 1: k_spmm_win everywhere, 3 (default): k_spmm_pipe where the block qualifies
     bool mm_dma = false;         // the last SpMM pass ran the pipelined kernel (bicg_spmm.hip)
 
+    // BICG_PLAN="reorder=1|2" (DESIGN.md section 4.14b): the diag block was renumbered before it was planned. Everything on the device is
+    // in the new numbering; the caller's vectors cross through perm / inv (vec_upload / vec_download below).
+    int reorder_mode = 0;                // the token's value (ctx_read_switches)
+    bool reordered = false;
+    uint32_t *ro_perm = nullptr, *ro_inv = nullptr;      // perm[new] = old, inv[old] = new
+    double *ro_stage = nullptr;          // staging for host copies: ro_stage_vecs vectors, `stride` apart; grows with the largest call
+    int ro_stage_vecs = 0;
+    unsigned long long ro_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // bicg_reorder_info
+    std::vector<uint32_t> ro_ptr, ro_col;                // the permuted block while bicg_create plans and uploads it
+    std::vector<double> ro_val;
+
     // state of the solve in progress (run_begin / run_iterate / run_end)
     bicg_options opt{};
     int method = 0, it = 0, printed = 0, adaptive_rr = 0;
@@ -322,6 +333,31 @@ inline double *host_out(bicg_ctx *c, double *p, size_t count = 1)
     if (!c->phantom || !p) return p;
     if (c->ph_scratch.size() < count) c->ph_scratch.assign(count, 0.0);
     return c->ph_scratch.data();
+}
+
+// A caller's vectors crossing into / out of device memory: nvec vectors of n_loc doubles, one after the other on the host,
+// dev_stride doubles apart on the device. async: enqueued on the compute stream (the caller synchronises before it returns);
+// otherwise blocking copies. A context that is not reordered does exactly these copies; a reordered one goes through its
+// staging buffer and the permutation kernels on the compute stream (reorder_upload / reorder_download, bicg_api.cpp).
+void reorder_upload(bicg_ctx *c, double *dev, size_t dev_stride, const double *host, int nvec, bool async);
+void reorder_download(bicg_ctx *c, double *host, const double *dev, size_t dev_stride, int nvec, bool async);
+inline void vec_upload(bicg_ctx *c, double *dev, size_t dev_stride, const double *host, int nvec = 1, bool async = false)
+{
+    if (c->reordered) { reorder_upload(c, dev, dev_stride, host, nvec, async); return; }
+    const size_t n = c->n_loc;
+    for (int j = 0; j < nvec; ++j) {
+        if (async) BICG_HIP(hipMemcpyAsync(dev + (size_t)j * dev_stride, host + (size_t)j * n, sizeof(double) * n, hipMemcpyHostToDevice, c->sc));
+        else BICG_HIP(hipMemcpy(dev + (size_t)j * dev_stride, host + (size_t)j * n, sizeof(double) * n, hipMemcpyHostToDevice));
+    }
+}
+inline void vec_download(bicg_ctx *c, double *host, const double *dev, size_t dev_stride, int nvec = 1, bool async = false)
+{
+    if (c->reordered) { reorder_download(c, host, dev, dev_stride, nvec, async); return; }
+    const size_t n = c->n_loc;
+    for (int j = 0; j < nvec; ++j) {
+        if (async) BICG_HIP(hipMemcpyAsync(host + (size_t)j * n, dev + (size_t)j * dev_stride, sizeof(double) * n, hipMemcpyDeviceToHost, c->sc));
+        else BICG_HIP(hipMemcpy(host + (size_t)j * n, dev + (size_t)j * dev_stride, sizeof(double) * n, hipMemcpyDeviceToHost));
+    }
 }
 
 inline void use_device(const bicg_ctx *c)

@@ -1,5 +1,6 @@
 // bicg_plan.h -- the plans that are made on the host without a device: the persistent iteration's (persist_plan_host,
-// bicg_plan.cpp) and the sliced-ELL plan of the diag block (sell_plan_host, bicg_sell_plan.cpp). Plain data: device vector
+// bicg_plan.cpp), the sliced-ELL plan of the diag block (sell_plan_host, bicg_sell_plan.cpp) and the renumbering of a badly
+// numbered diag block (reorder_rcm / permute_block, bicg_reorder.cpp). Plain data: device vector
 // types appear as element types only, nothing here calls the HIP runtime or reads the environment.
 #pragma once
 
@@ -103,5 +104,13 @@ bool sell_plan_host(const CSR_Matrix *diag, const uint32_t *optr, const PlanFact
 constexpr int kSellSummaryLen = 22, kSellDigestLen = 26;
 void sell_plan_summary(const SellPlan &plan, unsigned long long summary[kSellSummaryLen]);
 void sell_plan_digest(const SellPlan &plan, unsigned long long digest[kSellDigestLen]);
+
+// BICG_PLAN="reorder=1|2" (bicg_reorder.cpp; C views: bicg_reorder_plan / bicg_permute_block, include/bicgstab_hip.h section 5).
+// reorder_rcm: perm[new] = old, reverse Cuthill-McKee on the symmetrised pattern, and the eight stats of bicg_reorder_plan.
+// permute_block: P A P^T, the entries of a row in their stored order; inv_out (optional, rows entries): inv[old] = new. False
+// when perm is not a permutation of 0 .. rows - 1.
+void reorder_rcm(const CSR_Matrix *diag, uint32_t *perm, unsigned long long stats[8]);
+bool permute_block(const CSR_Matrix *diag, const uint32_t *perm, uint32_t *ptr_out, uint32_t *col_out, double *val_out,
+                   uint32_t *inv_out = nullptr);
 
 }  // namespace bicg

@@ -112,9 +112,8 @@ int run_switching(bicg_ctx *c, int mode, double *x_set_host, double *r_host, con
     BICG_HIP(hipMemcpy(h.sigma, sigma, sizeof(double) * nsig, hipMemcpyHostToDevice));
     BICG_HIP(hipMemset(c->p_set, 0, sizeof(double) * (size_t)nsig * st));
     BICG_HIP(hipMemset(c->x_set, 0, sizeof(double) * (size_t)nsig * st));
-    for (int j = 0; j < nsig; ++j)
-        BICG_HIP(hipMemcpy(c->x_set + (size_t)j * st, x_set_host + (size_t)j * n, sizeof(double) * n, hipMemcpyHostToDevice));
-    BICG_HIP(hipMemcpy(c->v.r, r_host, sizeof(double) * n, hipMemcpyHostToDevice));
+    vec_upload(c, c->x_set, st, x_set_host, nsig);
+    vec_upload(c, c->v.r, st, r_host);
     BICG_HIP(hipDeviceSynchronize());
 
     if (c->trace_cap < o.max_iter) {
@@ -204,9 +203,8 @@ int run_switching(bicg_ctx *c, int mode, double *x_set_host, double *r_host, con
     const int its = c->hS->k;
     c->last_iters = its;
     sec_collect(c, its);
-    for (int j = 0; j < nsig; ++j)
-        BICG_HIP(hipMemcpy(x_set_host + (size_t)j * n, c->x_set + (size_t)j * st, sizeof(double) * n, hipMemcpyDeviceToHost));
-    BICG_HIP(hipMemcpy(r_host, c->v.r, sizeof(double) * n, hipMemcpyDeviceToHost));
+    vec_download(c, x_set_host, c->x_set, st, nsig);
+    vec_download(c, r_host, c->v.r, st);
     if (res) {
         memset(res, 0, sizeof *res);
         res->iterations = its; res->dot_r = c->hS->dot_r; res->dot_zero = c->hS->dot_zero;
@@ -312,9 +310,8 @@ int run_shifted(bicg_ctx *c, int mode, double *x_set_host, double *r_host, const
     BICG_HIP(hipMemcpy(h.sigma, sigma, sizeof(double) * nsig, hipMemcpyHostToDevice));
     BICG_HIP(hipMemset(c->p_set, 0, sizeof(double) * (size_t)nsig * st));        // calloc, src/shifted_solver.c:223
     BICG_HIP(hipMemset(c->x_set, 0, sizeof(double) * (size_t)nsig * st));
-    for (int j = 0; j < nsig; ++j)
-        BICG_HIP(hipMemcpy(c->x_set + (size_t)j * st, x_set_host + (size_t)j * n, sizeof(double) * n, hipMemcpyHostToDevice));
-    BICG_HIP(hipMemcpy(c->v.r, r_host, sizeof(double) * n, hipMemcpyHostToDevice));
+    vec_upload(c, c->x_set, st, x_set_host, nsig);
+    vec_upload(c, c->v.r, st, r_host);
     BICG_HIP(hipDeviceSynchronize());       // the memsets above ran on the null stream; sc does not wait for it
 
     if (c->trace_cap < o.max_iter) {
@@ -426,9 +423,8 @@ int run_shifted(bicg_ctx *c, int mode, double *x_set_host, double *r_host, const
     const int k = c->hS->k;
     c->last_iters = k;
     sec_collect(c, k);
-    for (int j = 0; j < nsig; ++j)
-        BICG_HIP(hipMemcpy(x_set_host + (size_t)j * n, c->x_set + (size_t)j * st, sizeof(double) * n, hipMemcpyDeviceToHost));
-    BICG_HIP(hipMemcpy(r_host, c->v.r, sizeof(double) * n, hipMemcpyDeviceToHost));
+    vec_download(c, x_set_host, c->x_set, st, nsig);
+    vec_download(c, r_host, c->v.r, st);
     if (res) {
         memset(res, 0, sizeof *res);
         res->iterations = k; res->dot_r = c->hS->dot_r; res->dot_zero = c->hS->dot_zero;

@@ -62,6 +62,7 @@ EXPORTS = [
     "bicg_default_options", "bicg_create", "bicg_destroy", "bicg_solve", "bicg_load", "bicg_run", "bicg_fetch",
     "bicg_run_begin", "bicg_run_iterate", "bicg_run_iterate_timed", "bicg_run_end", "bicg_sync", "bicg_trace", "bicg_spmv", "bicg_dot", "bicg_spmv_bench", "bicg_plan_info", "bicg_ctx_flags", "bicg_spmm", "bicg_device_matrix_bytes", "bicg_uniform_entries", "bicg_constant_entries", "bicg_masked_rows", "bicg_stencil_info", "bicg_stencil_rows_per_lane", "bicg_comm_wait_stats", "bicg_plan_collisions", "bicg_product_kernels", "bicg_spmv_matrix_bytes", "bicg_last_shifted_persistent", "bicg_last_spmm_windowed", "bicg_dropin_context", "bicg_dropin_release", "bicg_dropin_stats",
     "bicg_mtx_load_block", "bicg_mtx_free", "bicg_partition", "bicg_halo_plan", "bicg_halo_send_counts", "bicg_halo_send_lists", "bicg_row_blocks", "bicg_window_plan", "bicg_window_slot", "bicg_version", "bicg_has_experiments", "bicg_switch_value", "bicg_switch_unknown", "bicg_stream_bench", "bicg_create_device_csr", "bicg_stencil7_device", "bicg_device_free", "bicg_persist_plan", "bicg_set_plan_threads", "bicg_sell_plan_digest",
+    "bicg_reorder_plan", "bicg_permute_block", "bicg_reorder_info",
 ]
 
 _lib = None
@@ -140,6 +141,9 @@ def lib():
         L.bicg_stencil7_device.argtypes = [C.c_uint, _dp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                            C.POINTER(C.c_ulonglong)]
         L.bicg_device_free.argtypes = [C.c_void_p]
+        L.bicg_reorder_plan.argtypes = [C.POINTER(CSRMatrix), C.c_int, _up, C.POINTER(C.c_ulonglong)]
+        L.bicg_permute_block.argtypes = [C.POINTER(CSRMatrix), _up, _up, _up, _dp]
+        L.bicg_reorder_info.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
         for name in ("bicgstab", "ca_bicgstab", "pipe_bicgstab"):
             getattr(L, name).argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp]
         L.pipe_bicgstab_rr.argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp,
@@ -151,7 +155,7 @@ def lib():
 # The library's token-list variables (csrc/bicg_knobs.h): keyword -> (variable, token). INTEGRATION.md section 6 says what each does.
 SWITCHES = {k: ("BICG_PLAN", k.replace("_", "-")) for k in (
     "stencil", "lines", "planes", "ca_fuse", "layout", "window", "col16", "uniform", "constant", "masked", "desc", "lists", "jagw",
-    "spmm", "spmm_window", "fuse_pipe", "pipe_probe", "halo_fused", "window_list", "wide")}
+    "spmm", "spmm_window", "fuse_pipe", "pipe_probe", "halo_fused", "window_list", "wide", "reorder")}
 SWITCHES.update(persist=("BICG_PERSIST", "0"), persist_chunk=("BICG_PERSIST", "chunk"), persist_shifted=("BICG_PERSIST", "shifted"),
                 force_comm=("BICG_TEST", "force-comm"), spin_ticks=("BICG_TEST", "spin-ticks"),
                 p2p_fault_after=("BICG_TEST", "p2p-fault-after"), plan_collide=("BICG_TEST", "plan-collide"))
@@ -434,7 +438,7 @@ class Context:
         return bool(lib().bicg_comm_failed(self.h))
 
     FLAGS = {"p2p": 1, "ll_fused": 2, "overlap": 4, "col16": 8, "all_sell": 16, "jagged": 32, "spmm": 64, "window": 128, "rowsplit": 256, "persist": 512,
-             "fuse_pipe": 1024, "pipe_probed": 2048, "uniform": 4096, "constant": 8192}
+             "fuse_pipe": 1024, "pipe_probed": 2048, "uniform": 4096, "constant": 8192, "reordered": 16384}
 
     def flags(self):
         f = int(lib().bicg_ctx_flags(self.h))
@@ -466,6 +470,14 @@ class Context:
         info = dict(zip(("on", "sy", "ny", "nz", "lines", "planes", "workgroups", "masked_segments"), list(out)))
         info["rows_per_lane"] = int(lib().bicg_stencil_rows_per_lane(self.h))
         return info
+
+    def reorder_info(self):
+        """the reordering bicg_create applied under BICG_PLAN="reorder=1|2" (bicg_reorder_info): dict keyed by REORDER_STATS with
+        `microseconds` = what ordering + permuting took, or None when this context is not reordered"""
+        out = (C.c_ulonglong * 8)()
+        if lib().bicg_reorder_info(self.h, out) != 0:
+            return None
+        return dict(zip(REORDER_STATS[:7] + ("microseconds",), (int(v) for v in out)))
 
     def plan_collisions(self) -> int:
         return int(lib().bicg_plan_collisions(self.h))
@@ -578,6 +590,36 @@ def sell_plan_digest(blocks: HostBlocks, nranks: int = 1, rows_global: int | Non
         raise RuntimeError("bicg_sell_plan_digest failed")
     del keep
     return dict(zip(SELL_SUMMARY, (int(v) for v in summ))), dict(zip(SELL_ARRAYS, (int(v) for v in dig)))
+
+
+# bicg_reorder_plan (include/bicgstab_hip.h section 5): names of its stats
+REORDER_STATS = ("rows", "components", "bandwidth_given", "bandwidth", "distinct_given", "distinct", "isolated_rows", "reserved")
+
+
+def reorder_plan(blocks: HostBlocks, method: int = 1):
+    """The renumbering bicg_create applies to this diag block under BICG_PLAN="reorder=1|2", without a GPU (bicg_reorder_plan):
+    (perm with perm[new] = old, stats dict keyed by REORDER_STATS). method 1: reverse Cuthill-McKee."""
+    perm = np.zeros(max(blocks.n_loc, 1), dtype=np.uint32)
+    stats = (C.c_ulonglong * 8)()
+    if lib().bicg_reorder_plan(C.byref(blocks.diag), method, perm.ctypes.data_as(_up), stats) != 0:
+        raise RuntimeError("bicg_reorder_plan failed")
+    return perm[:blocks.n_loc], dict(zip(REORDER_STATS, (int(v) for v in stats)))
+
+
+def permute_block(blocks: HostBlocks, perm) -> CSR:
+    """P A P^T of the diag block for perm[new] = old, the entries of every row in their stored order (bicg_permute_block);
+    ValueError when perm is not a permutation of 0 .. rows - 1"""
+    perm = np.ascontiguousarray(perm, dtype=np.uint32)
+    n, nz = blocks.n_loc, int(blocks.diag.ptr[blocks.diag.rows])
+    if perm.size != n:
+        raise ValueError("perm must have one entry per row")
+    ptr = np.zeros(n + 1, dtype=np.uint32)
+    col = np.zeros(max(nz, 1), dtype=np.uint32)
+    val = np.zeros(max(nz, 1))
+    up = lambda a: a.ctypes.data_as(_up)
+    if lib().bicg_permute_block(C.byref(blocks.diag), up(perm), up(ptr), up(col), _d(val)) != 0:
+        raise ValueError("perm is not a permutation of 0 .. rows - 1")
+    return CSR(n, n, ptr, col[:nz], val[:nz])
 
 
 def partition(n: int, nranks: int):
