@@ -342,7 +342,11 @@ enum { BICG_FLAG_P2P = 1, BICG_FLAG_LL_FUSED = 2, BICG_FLAG_OVERLAP = 4, BICG_FL
        BICG_FLAG_REORDERED = 16384 /* BICG_PLAN="reorder=1|2": bicg_create renumbered the diag block (P A P^T, reverse Cuthill-McKee,
                                      one rank only) before planning it; every vector the caller hands in or gets back crosses the
                                      permutation on the device, so the caller keeps its own numbering. The entries of a row keep
-                                     their stored order: products stay bit-identical to mult() on the caller's matrix */ };
+                                     their stored order: products stay bit-identical to mult() on the caller's matrix */,
+       BICG_FLAG_HANDOVER = 32768  /* plain BiCGStab on this context closes its dot groups by hand-over: the producing kernel leaves
+                                     shard totals, the kernel that consumes the scalars adds them and applies the recurrence
+                                     (one rank, padded 16-bit layout; BICG_PLAN="handover=0" selects the producer-side finish).
+                                     Same sums, same order: bit-identical */ };
 unsigned int bicg_ctx_flags(bicg_ctx *ctx);
 /* The reordering of a context with BICG_FLAG_REORDERED: the stats of bicg_reorder_plan (section 5) with out[7] = microseconds
  * bicg_create spent on ordering + permuting. Returns 0; 1 and zeros when the context is not reordered. */

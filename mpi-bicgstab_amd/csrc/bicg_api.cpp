@@ -342,6 +342,7 @@ unsigned int bicg_ctx_flags(bicg_ctx *c)
     if (c->uniform_entries) f |= BICG_FLAG_UNIFORM;
     if (c->constant_entries) f |= BICG_FLAG_CONSTANT;
     if (c->reordered) f |= BICG_FLAG_REORDERED;
+    if (plain_handover(c)) f |= BICG_FLAG_HANDOVER;
     return f;
 }
 

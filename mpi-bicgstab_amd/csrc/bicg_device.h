@@ -154,8 +154,14 @@ struct Reduce {
     llword   *tail_tab;    // [slots][kTailStride] LL words
     llword   *tail_shard;  // [kShards][kRedSlots][2]
     unsigned  tail_seq;
+    // Hand-over (RED_HAND, one GPU, plain BiCGStab): the tail finish ENDS with the shard totals -- the last min(expected, kShards)
+    // workgroups store them (tag tail_seq) into tail_shard, which then points at one of two alternating tables laid out
+    // [dot][kShards][2] (hand_index), and return; the kernel that consumes the scalars adds them and applies the recurrence
+    // in its prologue (hand_consume, bicg_reduce.h).
+    int       hand;
 };
 constexpr int kTailStride = 16;             // LL words per slot of the tail table (8 doubles)
+__host__ __device__ inline size_t hand_index(int d, unsigned shard) { return ((size_t)d * kShards + shard) * 2; }
 
 // ---- consumer-side finish of a dot group (the four solvers of reference src/solver.c) -------------
 // A kernel that PRODUCES dot sums only stores one partial per wavefront (wave shuffle, one plain
@@ -176,6 +182,8 @@ enum FinishRole : int {
     FIN_BLOCK0  = 8,   // workgroup 0 only, IN PLACE on S: SpMV launches (phase PH_NONE: the other workgroups
                        // read nothing but `done`) and the stand-alone finisher (any phase)
     FIN_LOCAL   = 16,  // with FIN_BLOCK0: deposit this rank's sums only (the host enqueues an all-reduce)
+    FIN_HAND    = 32,  // hand-over (RED_HAND), alone: every WAVEFRONT adds the nparts shard totals its producer left in `shard`
+                       // (tag seq, hand_index layout) and applies the functor's phase on a private copy; workgroup 0 writes Snext
 };
 struct Finish {
     const double *partial;   // [nparts][kPartialStride] one row per producing wavefront
@@ -195,7 +203,7 @@ struct Finish {
 
 // what every launch wrapper needs: the scalar block to read, the group to finish (if any), the
 // stream, and which reduction epilogue the kernel is built with
-enum RedMode : int { RED_TICKET = 0, RED_TICKET_HEAVY = 1, RED_WAVE = 2 };
+enum RedMode : int { RED_TICKET = 0, RED_TICKET_HEAVY = 1, RED_WAVE = 2, RED_HAND = 3 };
 struct Launch {
     Scal *S;
     Finish fin;

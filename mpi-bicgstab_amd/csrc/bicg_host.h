@@ -197,6 +197,16 @@ struct bicg_ctx {
     llword *tail_tab = nullptr, *tail_shard = nullptr;
     mutable unsigned tail_seq = 0;
     bool tail_finish = true;
+    // hand-over of plain BiCGStab's three dot groups (RED_HAND): the producer's tail finish stops at the shard totals, the kernel
+    // that consumes the scalars adds them and applies the recurrence. Two shard-total tables [kRedSlots][kShards][2] that alternate
+    // group by group (FPlainXR reads one group's totals while its last workgroups write the next group's), and the scalar blocks
+    // alternate as they do for the pipelined solvers (Sbuf / cur). BICG_PLAN="handover=0": the producer finishes the group itself.
+    bool handover = true;
+    llword *hand_shard = nullptr;
+    struct Hand {
+        unsigned seq = 0, nsh = 0;   // tag of the open group (0: none), shard totals its producer leaves
+        int n = 0, phase = 0, buf = 0;
+    } hand;
     unsigned nslots = 0;
     double *trace = nullptr;     // 4 * trace_cap
     int trace_cap = 0;
@@ -396,6 +406,7 @@ void group_now(bicg_ctx *c, int n, int phase);
 void group_defer(bicg_ctx *c, int n, int phase);
 void group_flush(bicg_ctx *c);
 bool stencil_product(const bicg_ctx *c);
+bool plain_handover(const bicg_ctx *c);      // plain BiCGStab on this context hands its dot groups over to the consuming kernels
 bool hosted(const bicg_ctx *c);      // several ranks whose collectives the host enqueues (RCCL / host transports)
 void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Reduce red, Finish fin = Finish{}, int epi = 0,
           Scal *S = nullptr);

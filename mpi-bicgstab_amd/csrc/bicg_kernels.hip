@@ -778,7 +778,7 @@ __device__ __forceinline__ void sell_halo_push(const SpmvArgs &a, unsigned bid, 
 }
 
 template <int NDOT, bool OFFD, bool NT, int LAY, bool LL, int MODE>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((MODE == RED_TICKET && LAY < LAY_PAD32C) ? 8 : 4, 8))) k_spmv_sell(SpmvArgs a)   // (layouts with list-driven slices: no pin, they spilled 200 bytes per lane at 64 registers)
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(((MODE == RED_TICKET || MODE == RED_HAND) && LAY < LAY_PAD32C) ? 8 : 4, 8))) k_spmv_sell(SpmvArgs a)   // (layouts with list-driven slices: no pin, they spilled 200 bytes per lane at 64 registers)
 {
     const int done = a.S->done;       // consumed at the stores only (see k_spmv)
     __shared__ double sm[5 * (NDOT > 0 ? NDOT : 1)];
@@ -943,7 +943,8 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu((MO
     }
     if (LL && ll_failed) { a.S->comm_error = 1; a.S->done = 1; }
     if (NDOT > 0 && !done) {
-        if (MODE == RED_WAVE) wave_publish<(NDOT > 0 ? NDOT : 1)>(acc, a.red.partial, a.red.slot_base + slot);
+        if constexpr (MODE == RED_WAVE) wave_publish<(NDOT > 0 ? NDOT : 1)>(acc, a.red.partial, a.red.slot_base + slot);
+        else if constexpr (MODE == RED_HAND) hand_publish<(NDOT > 0 ? NDOT : 1)>(acc, a.S, a.red, a.red.slot_base + slot, sm, a.red.slot_base + bid);
         else reduce_publish<(NDOT > 0 ? NDOT : 1), MODE == RED_TICKET_HEAVY>(acc, a.S, a.red, a.red.slot_base + slot, sm, a.red.slot_base + bid);
     }
 }
@@ -1116,7 +1117,11 @@ static bool sell_launch_layout(const SpmvArgs &a, int ndot, bool with_offd, hipS
         const bool nt = a.nt != 0;                                                                 \
         const int mode = red_mode(a.red, a.fin, (ND) > 0);                                         \
         constexpr int HV = (ND) > 0 ? RED_TICKET_HEAVY : RED_TICKET;                               \
-        if (mode == RED_WAVE) SELL_MODE(ND, OF, LLV, RED_WAVE);                                    \
+        if (mode == RED_HAND) {                                                                    \
+            /* hand-over: the padded 16-bit layout's products with dots, one rank (no offd, no exchange inside) */ \
+            if constexpr ((ND) > 0 && !(OF) && !(LLV) && LAY == LAY_PAD16) SELL_MODE(ND, OF, LLV, RED_HAND); \
+            else { fprintf(stderr, "ERROR: bicgstab_hip: no hand-over form of this sliced-ELL product\n"); abort(); } \
+        } else if (mode == RED_WAVE) SELL_MODE(ND, OF, LLV, RED_WAVE);                             \
         else if (mode == RED_TICKET_HEAVY) SELL_MODE(ND, OF, LLV, HV);                             \
         else SELL_MODE(ND, OF, LLV, RED_TICKET);                                                   \
     } while (0)
@@ -2098,6 +2103,8 @@ template <class F> struct vec_modes<F, decltype((void)F::kModes)> { static const
 template <class F, class = void> struct vec_split { static constexpr bool value = false; };
 template <class F> struct vec_split<F, decltype((void)F::kSplit)> { static constexpr bool value = F::kSplit; };
 constexpr int kWaveOnly = 1 << RED_WAVE, kAnyMode = (1 << RED_TICKET) | (1 << RED_TICKET_HEAVY) | (1 << RED_WAVE);
+// ... and the hand-over (plain BiCGStab's three element-wise kernels): F::kHandPhase / F::kHandN = the group the functor consumes
+constexpr int kHandMode = 1 << RED_HAND;
 
 // TILE > 0 (vectors far beyond the caches, vec_tiled()): a workgroup takes ONE contiguous tile of TILE pairs per thread -- 16 KiB
 // of every stream for TILE = 4 --, all loads of the tile are in flight before the first store, every access is non-temporal
@@ -2145,11 +2152,23 @@ __global__ void __launch_bounds__(kBlock) k_vec(F f, uint32_t n, Scal *S, Reduce
             f.load(sc);
             compute_tile();
             if (F::ND > 0) wave_publish<ND>(acc, red.partial, red.slot_base + blockIdx.x);
+        } else if constexpr (MODE == RED_HAND) {
+            Scal T;
+            fetch_tile();
+            hand_consume<F::kHandN, F::kHandPhase>(S, fin, T);
+            if (T.done) return;
+            f.load(&T);
+            compute_tile();
+            if constexpr (F::ND > 0) {
+                __shared__ double sm[5 * ND];
+                hand_publish<ND>(acc, fin.Snext, red, blockIdx.x, sm, blockIdx.x);
+            }
         } else {
+            // (the tile's loads depend on no scalar: they are in flight before `done` and the scalars are asked for)
+            fetch_tile();
             if (S->done) return;
             __shared__ double sm[5 * ND];
             f.load(S);
-            fetch_tile();
             compute_tile();
             if (F::ND > 0) reduce_publish<ND, MODE == RED_TICKET_HEAVY>(acc, S, red, blockIdx.x, sm);
         }
@@ -2181,11 +2200,39 @@ __global__ void __launch_bounds__(kBlock) k_vec(F f, uint32_t n, Scal *S, Reduce
         }
         if ((n & 1u) && blockIdx.x == 0 && threadIdx.x == 0) f.template apply<double>(n - 1, acc);
         if (F::ND > 0) wave_publish<ND>(acc, red.partial, red.slot_base + blockIdx.x);
+    } else if constexpr (MODE == RED_HAND) {
+        // hand-over: the first pair's loads, then the producer's shard totals and the scalar block in one batch; every wavefront
+        // adds the totals and applies the recurrence on its own copy (hand_consume) -- no LDS, no barrier in front of the loop
+        Scal T;
+        typename F::template In<d2> pre{};
+        const bool have = i0 < npair;
+        if (have) pre = f.template fetch<d2>(2 * i0);
+        hand_consume<F::kHandN, F::kHandPhase>(S, fin, T);
+        if (T.done) return;
+        f.load(&T);
+        if (have) f.template compute<d2>(2 * i0, pre, acc);
+        for (uint32_t i = i0 + stride; i < npair; i += stride) f.template compute<d2>(2 * i, f.template fetch<d2>(2 * i), acc);
+        if ((n & 1u) && blockIdx.x == 0 && threadIdx.x == 0) f.template apply<double>(n - 1, acc);
+        if constexpr (F::ND > 0) {
+            __shared__ double sm[5 * ND];
+            hand_publish<ND>(acc, fin.Snext, red, blockIdx.x, sm, blockIdx.x);
+        }
     } else {
-        if (S->done) return;
         __shared__ double sm[5 * ND];
-        f.load(S);
-        for (uint32_t i = i0; i < npair; i += stride) f.template apply<d2>(2 * i, acc);
+        if constexpr (vec_split<F>::value) {
+            // the first pair's loads depend on no scalar: they are in flight before `done` and the scalars are asked for
+            typename F::template In<d2> pre{};
+            const bool have = i0 < npair;
+            if (have) pre = f.template fetch<d2>(2 * i0);
+            if (S->done) return;
+            f.load(S);
+            if (have) f.template compute<d2>(2 * i0, pre, acc);
+            for (uint32_t i = i0 + stride; i < npair; i += stride) f.template compute<d2>(2 * i, f.template fetch<d2>(2 * i), acc);
+        } else {
+            if (S->done) return;
+            f.load(S);
+            for (uint32_t i = i0; i < npair; i += stride) f.template apply<d2>(2 * i, acc);
+        }
         if ((n & 1u) && blockIdx.x == 0 && threadIdx.x == 0) f.template apply<double>(n - 1, acc);
         if (F::ND > 0) reduce_publish<ND, MODE == RED_TICKET_HEAVY>(acc, S, red, blockIdx.x, sm);
     }
@@ -2246,6 +2293,17 @@ static void run_vec(F f, uint32_t n, const Launch &L, Reduce red)
         fprintf(stderr, "ERROR: bicgstab_hip: element-wise kernel launched in reduction mode %d it is not built for\n", mode);
         abort();
     }
+    if constexpr ((modes >> RED_HAND) & 1) {
+        if (mode == RED_HAND) {
+            if (!(L.fin.seq && (L.fin.roles & FIN_HAND)) || (F::ND > 0) != (red.hand != 0)) {
+                fprintf(stderr, "ERROR: bicgstab_hip: hand-over launch without the group it consumes / produces\n");
+                abort();
+            }
+            if (vec_tiled(n)) BICG_LAUNCH((k_vec<F, RED_HAND, kVecTile>), dim3(g), dim3(kBlock), 0, L.st, f, n, L.S, red, L.fin);
+            else BICG_LAUNCH((k_vec<F, RED_HAND>), dim3(g), dim3(kBlock), 0, L.st, f, n, L.S, red, L.fin);
+            return;
+        }
+    }
     if constexpr (vec_split<F>::value) {
         if (vec_tiled(n)) {
             if constexpr ((modes >> RED_WAVE) & 1)
@@ -2294,7 +2352,8 @@ void launch_init_residual(const Vecs &v, bool copy_p, bool save_b, const Launch 
 // ---- plain: q = r - alpha s (kept in r)                               (src/solver.c:94)
 struct FPlainQ {
     static constexpr int ND = 0;
-    static constexpr int kModes = kAnyMode;
+    static constexpr int kModes = kAnyMode | kHandMode;
+    static constexpr int kHandPhase = PH_PLAIN_ALPHA, kHandN = 1;
     static constexpr bool kSplit = true;
     double *r; const double *s; double alpha;
     template <class T> struct In { T r, s; };
@@ -2311,7 +2370,8 @@ void launch_plain_q(const Vecs &v, const Launch &L) { run_vec(FPlainQ{v.r, v.s, 
 // ---- plain: x += alpha p + omega q ; r = q - omega y ; (r,r), (r#,r)   (src/solver.c:105-111)
 template <bool XNT> struct FPlainXR {
     static constexpr int ND = 2;
-    static constexpr int kModes = kAnyMode;
+    static constexpr int kModes = kAnyMode | kHandMode;
+    static constexpr int kHandPhase = PH_OMEGA, kHandN = 2;
     static constexpr bool kSplit = true;
     double *x, *r; const double *q, *p, *y, *rh; double alpha, omega;      // q: where q lives (r itself, or the fused iteration's own buffer)
     template <class T> struct In { T q, x, p, y, rh; };
@@ -2341,7 +2401,8 @@ void launch_plain_xr(const Vecs &v, const Launch &L, Reduce red, const double *q
 // ---- plain: p = beta p ; p += r ; p += (-beta*omega) s                (src/solver.c:117-119)
 struct FPlainP {
     static constexpr int ND = 0;
-    static constexpr int kModes = kAnyMode;
+    static constexpr int kModes = kAnyMode | kHandMode;
+    static constexpr int kHandPhase = PH_PLAIN_END, kHandN = 2;
     static constexpr bool kSplit = true;
     double *p; const double *r, *s; double beta, c;
     template <class T> struct In { T p, r, s; };

@@ -253,6 +253,116 @@ __device__ __forceinline__ unsigned shard_population(unsigned expected, unsigned
     return shard < expected ? (expected - shard + kShards - 1) / kShards : 0u;
 }
 
+// Tail finish, first level (struct Reduce): the workgroup's partial goes into the LL table; all but the last min(expected, kShards)
+// workgroups of the launch leave (false). Those stay, add one shard of the table each (slots sh, sh + nsh, ... in order) and
+// return true with the shard's totals in tot[] on every thread. Serr: the scalar block in which a give-up is recorded.
+template <int ND>
+__device__ __forceinline__ bool tail_shard_sum(double (&acc)[ND], Scal *Serr, const Reduce &red, unsigned slot, unsigned order, double *sm,
+                                               double (&tot)[ND], unsigned &sh)
+{
+    const unsigned seq = red.tail_seq, nsh = red.expected < (unsigned)kShards ? red.expected : (unsigned)kShards;
+    if (threadIdx.x < ND) ll_store_agent(red.tail_tab + (size_t)slot * kTailStride + 2 * threadIdx.x, acc[threadIdx.x], seq);
+    if (order + nsh < red.expected) return false;
+    sh = red.expected - 1u - order;                                      // this workgroup's shard: 0 = the very last workgroup
+    const unsigned long long patience = 400000000ull;                   // 4 s: a lost workgroup must not hang the GPU
+#pragma unroll
+    for (int d = 0; d < ND; ++d) tot[d] = 0.0;
+    bool lost = false;
+    for (unsigned i = sh + threadIdx.x * nsh; i < red.expected && !lost; i += kBlock * nsh) {     // slots sh, sh + nsh, ... in order
+        const llword *row = red.tail_tab + (size_t)i * kTailStride;
+        const unsigned long long t0 = wall_clock64();
+        for (unsigned spin = 0;; ++spin) {
+            double v[ND];
+            bool all = true;
+#pragma unroll
+            for (int d = 0; d < ND; ++d) all = ll_peek_agent(row + 2 * d, seq, &v[d]) && all;
+            if (all) {
+#pragma unroll
+                for (int d = 0; d < ND; ++d) tot[d] += v[d];
+                break;
+            }
+            __builtin_amdgcn_s_sleep(8);
+            if ((spin & 63u) == 63u && wall_clock64() - t0 > patience) { lost = true; break; }
+        }
+    }
+    // a producer that never delivered: the error is raised by the very thread that gave up (any thread of any shard
+    // workgroup, not only thread 0 of the last one), and its shard total is poisoned -- a NaN cannot pass for a sum
+    if (lost) { Serr->comm_error = 1; Serr->done = 1; tot[0] = __builtin_nan(""); }
+    block_sum<ND>(tot, sm);
+    return true;
+}
+
+// Producer epilogue of the hand-over (RED_HAND): the tail finish up to the shard totals and nothing behind them -- no final
+// level, no Scal::red, no recurrence, no tickets, no peer-to-peer. The consuming kernel's prologue does the rest (hand_consume).
+template <int ND>
+__device__ __forceinline__ void hand_publish(double (&acc)[ND], Scal *Serr, const Reduce &red, unsigned slot, double *sm, unsigned order)
+{
+    block_sum<ND>(acc, sm);
+    double tot[ND];
+    unsigned sh = 0;
+    if (!tail_shard_sum<ND>(acc, Serr, red, slot, order, sm, tot, sh)) return;
+    if (threadIdx.x < ND) ll_store_agent(red.tail_shard + hand_index((int)threadIdx.x, sh), tot[threadIdx.x], red.tail_seq);
+}
+
+// A scalar block copied field by field: a private copy then lives in registers (wave-uniform fields of a block in global memory
+// arrive as scalar loads), where a whole-struct copy goes through 48 vector registers or scratch.
+__device__ __forceinline__ void scal_copy(Scal &d, const Scal &s)
+{
+    static_assert(sizeof(Scal) == 192, "scal_copy lists every field of Scal");
+    d.alpha = s.alpha; d.beta = s.beta; d.omega = s.omega; d.rTr = s.rTr; d.rTr_old = s.rTr_old;
+    d.dot_r = s.dot_r; d.dot_zero = s.dot_zero; d.tol2 = s.tol2;
+#pragma unroll
+    for (int i = 0; i < kRedSlots; ++i) d.red[i] = s.red[i];
+    d.k = s.k; d.max_iter = s.max_iter; d.done = s.done; d.breakdown_k = s.breakdown_k;
+    d.tr_alpha = s.tr_alpha; d.tr_omega = s.tr_omega; d.tr_beta = s.tr_beta; d.tr_dotr = s.tr_dotr;
+    d.sh = s.sh; d.comm_error = s.comm_error; d.paused = s.paused;
+}
+__device__ __forceinline__ double wave_uniform(double v)      // a value every lane holds, moved to scalar registers
+{
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
+// Consumer prologue of the hand-over, run by EVERY wavefront without LDS or barrier: lane l < nsh takes shard l's totals (one
+// 16-byte load per dot; the kernel boundary behind the producer guarantees they are there), the sums are formed with the
+// association of the tail finish's last block_sum -- wave_sum over 64 lanes, zeros beyond nsh, then + the three zero sums of the
+// other wavefronts --, and the phase runs on the private copy T of *S. One lane of workgroup 0 writes T to f.Snext, the block the
+// host reads from now on (also when the solve is `done`: the host switches blocks regardless), and alone touches the trace.
+// A wrong tag is a producer that never delivered: comm_error, done, a NaN for a sum.
+template <int N, int PHASE>
+__device__ __forceinline__ void hand_consume(const Scal *S, const Finish &f, Scal &T)
+{
+    const unsigned lane = threadIdx.x & 63u, nsh = f.nparts;
+    unsigned long long w0[N], w1[N];
+#pragma unroll
+    for (int d = 0; d < N; ++d) {
+        const ulonglong2 q = *reinterpret_cast<const ulonglong2 *>(f.shard + hand_index(d, lane & (unsigned)(kShards - 1)));
+        w0[d] = q.x; w1[d] = q.y;
+    }
+    scal_copy(T, *S);
+    const bool pub = blockIdx.x == 0 && threadIdx.x == 0;
+    if (T.done) {            // converged: the producer wrote nothing, nothing may change any more
+        if (pub) scal_copy(*f.Snext, T);
+        return;
+    }
+    double tot[N];
+    bool bad = false;
+#pragma unroll
+    for (int d = 0; d < N; ++d) {
+        const bool mine = lane < nsh;
+        bad = bad || (mine && !((unsigned)(w0[d] >> 32) == f.seq && (unsigned)(w1[d] >> 32) == f.seq));
+        const double v = mine ? __longlong_as_double((long long)((w0[d] & 0xffffffffull) | (w1[d] << 32))) : 0.0;
+        double s = wave_sum(v);
+        s += 0.0; s += 0.0; s += 0.0;      // the other three wavefronts of the last block_sum
+        tot[d] = s;
+    }
+    if (__ballot(bad) != 0ull) { T.comm_error = 1; T.done = 1; tot[0] = __builtin_nan(""); }
+#pragma unroll
+    for (int d = 0; d < N; ++d) T.red[d] = tot[d];
+    apply_phase(&T, PHASE, pub);
+    if (pub) scal_copy(*f.Snext, T);
+    T.alpha = wave_uniform(T.alpha); T.beta = wave_uniform(T.beta); T.omega = wave_uniform(T.omega);      // what the functors read
+}
+
 template <int ND, bool HEAVY>
 __device__ __forceinline__ void reduce_publish(double (&acc)[ND], Scal *S, const Reduce &red, unsigned slot, double *sm,
                                                unsigned order = 0xFFFFFFFFu)
@@ -268,35 +378,11 @@ __device__ __forceinline__ void reduce_publish(double (&acc)[ND], Scal *S, const
     if (!HEAVY && red.tail_seq) {
         // ---- tail finish: LL-tagged partials, producers leave at once (struct Reduce)
         const unsigned seq = red.tail_seq, nsh = red.expected < (unsigned)kShards ? red.expected : (unsigned)kShards;
-        if (threadIdx.x < ND) ll_store_agent(red.tail_tab + (size_t)slot * kTailStride + 2 * threadIdx.x, acc[threadIdx.x], seq);
-        if (order + nsh < red.expected) return;
-        const unsigned sh = red.expected - 1u - order;                       // this workgroup's shard: 0 = the very last workgroup
-        const unsigned long long patience = 400000000ull;                   // 4 s: a lost workgroup must not hang the GPU
+        const unsigned long long patience = 400000000ull;
         double tot[ND];
-#pragma unroll
-        for (int d = 0; d < ND; ++d) tot[d] = 0.0;
+        unsigned sh = 0;
         bool lost = false;
-        for (unsigned i = sh + threadIdx.x * nsh; i < red.expected && !lost; i += kBlock * nsh) {     // slots sh, sh + nsh, ... in order
-            const llword *row = red.tail_tab + (size_t)i * kTailStride;
-            const unsigned long long t0 = wall_clock64();
-            for (unsigned spin = 0;; ++spin) {
-                double v[ND];
-                bool all = true;
-#pragma unroll
-                for (int d = 0; d < ND; ++d) all = ll_peek_agent(row + 2 * d, seq, &v[d]) && all;
-                if (all) {
-#pragma unroll
-                    for (int d = 0; d < ND; ++d) tot[d] += v[d];
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(8);
-                if ((spin & 63u) == 63u && wall_clock64() - t0 > patience) { lost = true; break; }
-            }
-        }
-        // a producer that never delivered: the error is raised by the very thread that gave up (any thread of any shard
-        // workgroup, not only thread 0 of the last one), and its shard total is poisoned -- a NaN cannot pass for a sum
-        if (lost) { S->comm_error = 1; S->done = 1; tot[0] = __builtin_nan(""); }
-        block_sum<ND>(tot, sm);
+        if (!tail_shard_sum<ND>(acc, S, red, slot, order, sm, tot, sh)) return;
         if (threadIdx.x < ND) ll_store_agent(red.tail_shard + ((size_t)sh * kRedSlots + threadIdx.x) * 2, tot[threadIdx.x], seq);
         if (sh != 0) return;
 #pragma unroll
@@ -605,6 +691,7 @@ __device__ __forceinline__ const Scal *finish_group(Scal *S, const Finish &f, in
 // which reduction epilogue / prologue a launch needs (RedMode)
 static inline int red_mode(const Reduce &red, const Finish &fin, bool has_dots)
 {
+    if ((fin.seq && (fin.roles & FIN_HAND)) || (has_dots && red.hand)) return RED_HAND;
     if (fin.seq || (has_dots && red.wave)) return RED_WAVE;
     return has_dots && heavy_needed(red) ? RED_TICKET_HEAVY : RED_TICKET;
 }

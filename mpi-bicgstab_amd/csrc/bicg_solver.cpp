@@ -282,6 +282,7 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
     red.expected = merged ? g_sall + g_ci + g_cb : g_si + g_ci + g_sb + g_cb;
     red.slot_base = 0;
     a.red = red;
+    if (red.hand) c->hand.nsh = std::min<unsigned>(red.expected, (unsigned)kShards);      // what the consuming kernel will find
     if (red.wave && (ndot > 0 || epi)) c->grp.nparts = red.expected * (kBlock / 64);   // one partial per wavefront
 
     // per-kernel timing: every SpMV kernel of this call gets its own start/stop event pair
@@ -566,6 +567,17 @@ void group_flush(bicg_ctx *c)
 void fetch_scal(bicg_ctx *c);
 
 
+// Hand-over of plain BiCGStab's dot groups (struct Reduce / FIN_HAND): one rank, tail finish, eager launches, and every product of
+// the iteration a single launch of k_spmv_sell on padded slices with 16-bit offsets and streamed values -- the layout whose
+// product the hand-over epilogue leaves without scratch at eight wavefronts per SIMD (tests/test_handover_resources.py; the
+// 32-bit layout keeps 12 bytes of it with two dots, the list-driven ones run at five or six wavefronts whatever their epilogue).
+bool plain_handover(const bicg_ctx *c)
+{
+    return c->handover && c->single() && !c->p2p && c->tail_finish && c->tail_tab && c->hand_shard && c->graph_mode != 1 &&
+           c->nblk == 0 && c->glist_all && c->sell_entries > 0 && !c->sell_jag && !c->win_slots && c->s_col16 && !c->s_vbase &&
+           c->ng_bnd == 0 && c->n_int == 0 && c->n_bnd == 0 && !stencil_product(c);
+}
+
 // ---------------------------------------------------------------- the four iterations
 struct Driver {
     bicg_ctx *c;
@@ -614,8 +626,46 @@ struct Driver {
         group_flush(c);
     }
 
+    bool handover() const { return plain_handover(c); }
+    // the producer's side: its last workgroups leave the shard totals in the table the previous group does not use
+    Reduce hand_produce(int phase, int n)
+    {
+        Reduce r = c->red(0, phase, true, n);
+        bicg_ctx::Hand &h = c->hand;
+        h.buf ^= 1; h.seq = r.tail_seq; h.n = n; h.phase = phase;
+        r.hand = 1; r.apply_now = 0;
+        r.tail_shard = c->hand_shard + (size_t)h.buf * kRedSlots * kShards * 2;
+        return r;
+    }
+    // the consumer's side: it reads the current scalar block and the open group's totals and writes the other block, which is
+    // what everything enqueued from now on (and the host) reads
+    Launch hand_consume()
+    {
+        const bicg_ctx::Hand &h = c->hand;
+        if (!h.seq) die("internal", "hand-over: a consumer without an open dot group");
+        Launch L{c->S, Finish{}, c->sc};
+        L.fin.seq = h.seq; L.fin.nparts = h.nsh; L.fin.n = h.n; L.fin.red_off = 0; L.fin.phase = h.phase; L.fin.roles = FIN_HAND;
+        L.fin.shard = c->hand_shard + (size_t)h.buf * kRedSlots * kShards * 2;
+        c->cur ^= 1;
+        c->S = c->Sbuf + c->cur;
+        L.fin.Snext = c->S;
+        c->hand.seq = 0;
+        return L;
+    }
+
     void iter_plain()   // reference src/solver.c:88-119
     {
+        if (handover()) {
+            spmv(c, v.p, v.s, 1, v.rh, hand_produce(PH_PLAIN_ALPHA, 1));      // s = A p, (r#,s)
+            launch_plain_q(v, hand_consume());                                // -> alpha ; q = r - alpha s
+            spmv(c, v.r, v.y, 2, v.r, hand_produce(PH_OMEGA, 2));             // y = A q, (q,y), (y,y)
+            const Launch L = hand_consume();                                  // -> omega ; x, r, (r,r), (r#,r)
+            const Reduce r = hand_produce(PH_PLAIN_END, 2);
+            c->hand.nsh = std::min<unsigned>(vg, (unsigned)kShards);
+            launch_plain_xr(v, L, r);
+            launch_plain_p(v, hand_consume());                                // -> beta, k++ ; p = r + beta (p - omega s)
+            return;
+        }
         spmv(c, v.p, v.s, 1, v.rh, c->red(0, PH_PLAIN_ALPHA, true, 1));   // s = A p, (r#,s) -> alpha
         group_now(c, 1, PH_PLAIN_ALPHA);
         launch_plain_q(v, here());                              // q = r - alpha s

@@ -155,7 +155,7 @@ def lib():
 # The library's token-list variables (csrc/bicg_knobs.h): keyword -> (variable, token). INTEGRATION.md section 6 says what each does.
 SWITCHES = {k: ("BICG_PLAN", k.replace("_", "-")) for k in (
     "stencil", "lines", "planes", "ca_fuse", "layout", "window", "col16", "uniform", "constant", "masked", "desc", "lists", "jagw",
-    "spmm", "spmm_window", "fuse_pipe", "pipe_probe", "halo_fused", "window_list", "wide", "reorder")}
+    "spmm", "spmm_window", "fuse_pipe", "pipe_probe", "halo_fused", "window_list", "wide", "reorder", "handover")}
 SWITCHES.update(persist=("BICG_PERSIST", "0"), persist_chunk=("BICG_PERSIST", "chunk"), persist_shifted=("BICG_PERSIST", "shifted"),
                 force_comm=("BICG_TEST", "force-comm"), spin_ticks=("BICG_TEST", "spin-ticks"),
                 p2p_fault_after=("BICG_TEST", "p2p-fault-after"), plan_collide=("BICG_TEST", "plan-collide"))
@@ -438,7 +438,7 @@ class Context:
         return bool(lib().bicg_comm_failed(self.h))
 
     FLAGS = {"p2p": 1, "ll_fused": 2, "overlap": 4, "col16": 8, "all_sell": 16, "jagged": 32, "spmm": 64, "window": 128, "rowsplit": 256, "persist": 512,
-             "fuse_pipe": 1024, "pipe_probed": 2048, "uniform": 4096, "constant": 8192, "reordered": 16384}
+             "fuse_pipe": 1024, "pipe_probed": 2048, "uniform": 4096, "constant": 8192, "reordered": 16384, "handover": 32768}
 
     def flags(self):
         f = int(lib().bicg_ctx_flags(self.h))
