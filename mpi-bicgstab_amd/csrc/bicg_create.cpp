@@ -450,7 +450,7 @@ void bicg_default_options(bicg_options *o)
     o->check_every = 16;
 }
 
-// the code objects this context launches from, loaded now (preload_kernels, bicg_kernels.hip)
+// the code objects this context launches from, loaded now (preload_kernels, bicg_spmv_sell.hip)
 static void preload_for(bicg_ctx *c)
 {
     if (knob_x("BICG_PRELOAD") && atoi(knob_x("BICG_PRELOAD")) == 0) return;

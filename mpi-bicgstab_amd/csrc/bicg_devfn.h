@@ -1,4 +1,4 @@
-// bicg_devfn.h -- device functions shared by the kernel translation units (bicg_kernels.hip, bicg_persist.hip):
+// bicg_devfn.h -- device functions shared by the kernel translation units (bicg_spmv_*.hip, bicg_vec.hip, bicg_persist.hip, ...):
 // the scalar recurrences of the four solvers, LL words (payload + sequence tag in one 8-byte store), DPP wavefront sums.
 // gfx950 only; compiled with -ffp-contract=off like everything else.
 #pragma once
@@ -6,6 +6,8 @@
 #include "bicg_device.h"
 
 namespace bicg {
+
+typedef double f64x2 __attribute__((ext_vector_type(2)));      // one 16-byte access (bicg_vec.hip, bicg_spmm_sell.hip)
 
 // ------------------------------------------------------------------------------------------
 // scalar recurrences (one thread)
@@ -217,7 +219,7 @@ __device__ __forceinline__ void shift_omega_coeffs(ShiftDev *H, int j, double w_
     H->zeta[j] = (1.0 - w_seed * dsg) * z;                           // (:300)
 }
 
-// MAXT >= blockDim.x (a power of two); kernels of bicg_kernels.hip call it with 256 threads, the persistent kernels' helper
+// MAXT >= blockDim.x (a power of two); the one-launch-per-phase kernels call it with 256 threads, the persistent kernels' helper
 // workgroup with up to 1024. The only reduction is a maximum: the result does not depend on the number of threads.
 template <int MAXT>
 __device__ __forceinline__ void apply_phase_shifted(Scal *S, int phase, double *smax_buf = nullptr /* [MAXT] LDS, or the static one */)

@@ -1,5 +1,5 @@
 // bicg_device.h -- device-side state and kernel launch interface shared by the kernels
-// (bicg_kernels.hip) and the host side (bicg_solver.cpp, bicg_shifted.cpp, bicg_create.cpp: bicg_host.h). gfx950 only.
+// (bicg_spmv_*.hip, bicg_vec.hip, bicg_exchange.hip, ...) and the host side (bicg_solver.cpp, bicg_shifted.cpp, bicg_create.cpp: bicg_host.h). gfx950 only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -481,7 +481,7 @@ constexpr int kPersistMaxShifts = 32;
 unsigned persist_lds_bytes(const PersistArgs &a);
 constexpr unsigned kPersistMaxLds = 160u * 1024u - 1024u;     // dynamic LDS a launch may ask for (static part: < 1 KiB)
 
-// Sliced-ELL SpMM over kSpmmCols vectors held row-major (bicg_kernels.hip, k_spmm_sell)
+// Sliced-ELL SpMM over kSpmmCols vectors held row-major (bicg_spmm_sell.hip, k_spmm_sell)
 constexpr int kSpmmCols = 16;
 struct SpmmArgs {
     SellDev sell;
@@ -515,14 +515,30 @@ enum ProductKernel : unsigned { PK_SELL_PAD = 1, PK_SELL_JAG = 2, PK_SELL_WINLOO
                                 PK_SELL_EPI = 128, PK_JAGD = 512, PK_JAGW_LIST = 1024 };
 extern unsigned g_product_kernels;
 
-// ---- launch wrappers (bicg_kernels.hip) ----
+// ---- launch wrappers, by the unit that defines them ----
+// bicg_spmv_csr.hip
 // Both return false when there was nothing to launch. e0/e1 (optional): start/stop events bound to
 // this one kernel (hipExtLaunchKernelGGL) -- the per-kernel durations bench.py's roofline uses.
 bool launch_spmv(const SpmvArgs &a, int ndot, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);        // CSR row-block stream
+unsigned spmv_grid(uint32_t nlist);   // workgroups used by the CSR SpMV for nlist row blocks
+void preload_csr_kernels();
+// bicg_spmv_sell.hip (the layouts' kernels: bicg_spmv_sell_lay.hip, one translation unit per layout)
 bool launch_spmv_sell(const SpmvArgs &a, int ndot, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
                       bool fused_halo = false);   // sliced ELL; fused_halo: a.ll describes the in-kernel exchange
+// SpMV + pipelined phase in the epilogue (epi 1: phase 2 after v = A z; epi 2: phase 1 after t = A w); a.fin is
+// applied at the epilogue, a.red receives the phase's dot partials
+bool launch_spmv_sell_epi(const SpmvArgs &a, int epi, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
+                          bool fused_halo = false);
+unsigned sell_grid(uint32_t ngroups, int per_wg); // workgroups launched for ngroups 256-row groups
+// look up one kernel of every translation unit a context with this sliced-ELL plan launches from (loads their code objects now)
+void preload_kernels(const SellDev &d, bool sell);
+// bicg_stencil.hip
 // plane-marching product of a 7-point grid stencil (bicg_stencil.hip; a.sell.st.on). epi = 1: CA-BiCGStab's q = r - alpha s,
 // y = w - alpha z, (q,y), (y,y) (reference src/solver.c:225-232) on the wavefront's own rows behind z = A s (a.epi.r / a.epi.w)
+unsigned stencil_grid(const StencilDev &st);
+bool launch_spmv_stencil(const SpmvArgs &a, int ndot, int epi, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+void preload_stencil_kernels();
+// bicg_jagw.hip
 // the ragged-rows product with three dependent trips per group (bicg_jagw.hip); jagw_fast_ok: this launch qualifies
 bool jagw_fast_ok(const SpmvArgs &a, bool with_offd, bool fused_halo);
 bool launch_spmv_jagw(const SpmvArgs &a, int ndot, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
@@ -530,36 +546,32 @@ bool launch_spmv_jagw(const SpmvArgs &a, int ndot, hipStream_t st, hipEvent_t e0
 bool jagd_fast_ok(const SpmvArgs &a, bool with_offd, bool fused_halo);
 bool launch_spmv_jagd(const SpmvArgs &a, int ndot, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 void preload_jagw_kernels();
-unsigned stencil_grid(const StencilDev &st);
-bool launch_spmv_stencil(const SpmvArgs &a, int ndot, int epi, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-void preload_stencil_kernels();
+// bicg_spmm_sell.hip
 void launch_spmm_sell(const SpmmArgs &a, bool with_offd, hipStream_t st);
 // vectors per LDS window of the windowed form for `wslots` doubles per vector (0: the window does not fit, use launch_spmm_sell)
 int spmm_win_vectors(unsigned wslots);
 hipError_t launch_spmm_win(const SpmmArgs &a, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);   // e0 / e1: stamped at the kernel's start / end
+unsigned spmm_grid(uint32_t ngroups, bool xcd_map);
+void launch_colsum(const double *partial, unsigned nwg, double *out, hipStream_t st);          // out[col] = sum_wg partial[wg][col]
+void launch_rows_from_vectors(const double *x, size_t stride, int nvec, uint32_t n, double *xt, hipStream_t st);
+void launch_vectors_from_rows(const double *yt, size_t stride, int nvec, uint32_t n, double *y, hipStream_t st);
+void preload_spmm_sell_kernels();
+// bicg_spmm.hip, bicg_spmm_jag.hip
 // pipelined form (bicg_spmm.hip, k_spmm_pipe): the window of the next step copied global -> LDS by the DMA path while the current one
 // multiplies, persistent workgroups over consecutive groups; padded 16-bit layouts with clusters (hipErrorInvalidValue: not this block)
 hipError_t launch_spmm_pipe(const SpmmArgs &a, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 // the same pipeline on jagged slices with x windows (bicg_spmm_jag.hip, k_spmm_jpipe); hipErrorInvalidValue: the block does not qualify
 hipError_t launch_spmm_jpipe(const SpmmArgs &a, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 void preload_spmm_kernels();
-unsigned spmm_grid(uint32_t ngroups, bool xcd_map);
-// look up one kernel of every translation unit a context with this sliced-ELL plan launches from (loads their code objects now)
-void preload_kernels(const SellDev &d, bool sell);
+// bicg_persist.hip
 void preload_persist_kernels();
-void launch_colsum(const double *partial, unsigned nwg, double *out, hipStream_t st);          // out[col] = sum_wg partial[wg][col]
-void launch_rows_from_vectors(const double *x, size_t stride, int nvec, uint32_t n, double *xt, hipStream_t st);
-void launch_vectors_from_rows(const double *yt, size_t stride, int nvec, uint32_t n, double *y, hipStream_t st);
+// bicg_reorder.hip
 // a reordered context's vectors crossing the permutation (bicg_reorder.hip), nvec vectors in one launch:
 // in: dst[j][new] = src[j][perm[new]]; out: dst[j][old] = src[j][inv[old]] -- gathers with coalesced stores either way
 void launch_permute_in(const double *src, size_t src_stride, double *dst, size_t dst_stride, const uint32_t *perm, uint32_t n, int nvec, hipStream_t st);
 void launch_permute_out(const double *src, size_t src_stride, double *dst, size_t dst_stride, const uint32_t *inv, uint32_t n, int nvec, hipStream_t st);
-// SpMV + pipelined phase in the epilogue (epi 1: phase 2 after v = A z; epi 2: phase 1 after t = A w); a.fin is
-// applied at the epilogue, a.red receives the phase's dot partials
-bool launch_spmv_sell_epi(const SpmvArgs &a, int epi, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
-                          bool fused_halo = false);
+// bicg_exchange.hip
 void launch_apply(Scal *S, int phase, hipStream_t st);
-void launch_finish(const Launch &L);   // stand-alone finisher: L.fin with FIN_BLOCK0
 void launch_halo_pack(const double *x, const uint32_t *send_idx, uint32_t nsend, double *sendbuf, Scal *S, hipStream_t st);
 // peer-to-peer transport: wait for the P contributions of group pr.seq, sum n values, apply `phase`
 void launch_apply_p2p(Scal *S, int phase, int n, const P2pRed &pr, unsigned long long timeout_ticks, hipStream_t st);
@@ -581,7 +593,10 @@ void launch_p2p_selftest(const P2pRed &pr, unsigned seq0, int rounds, unsigned l
 // kHaloRing - 2 rounds; status[0] counts wrong / stale values, status[1] time-outs
 void launch_p2p_ringtest(const P2pRed &pr, llword *const *rings, int entries, unsigned seq0, int rounds, unsigned bar_seq0,
                          unsigned long long timeout_ticks, int *status, hipStream_t st);
+void preload_exchange_kernels();
 
+// bicg_vec.hip
+void launch_finish(const Launch &L);   // stand-alone finisher: L.fin with FIN_BLOCK0
 // The kernels of the four solvers take a Launch: the scalar block to read, the dot group of earlier
 // kernels to finish first (if any) and the stream.
 // init: r = b - Ax ; rh = r ; [p = r] ; [bsave = b] ; dot (r,r)
@@ -626,6 +641,9 @@ void launch_scale(double *x, uint32_t n, double a, hipStream_t st);             
 void launch_drift(const Vecs &v, const Launch &L, Reduce red);
 // standalone dot (x,y) -> red[0]
 void launch_dot(const double *x, const double *y, uint32_t n, Scal *S, Reduce red, hipStream_t st);
+unsigned vec_grid(uint32_t n);        // workgroups used by the element-wise kernels for length n
+void set_vec_grid_cap(unsigned cap);  // ranks sharing one GPU (tests): fewer workgroups per launch (0 = default)
+void preload_vec_kernels();
 
 // device-side sliced-ELL plan (bicg_plan_device.hip): slice lengths + "some column is further than 32767 from its row",
 // then the column-major padded copy (32-bit columns or packed 16-bit offsets)
@@ -642,9 +660,5 @@ void launch_plan_verify(const uint32_t *ptr, const uint32_t *col, const double *
 void launch_plan_fill(const uint32_t *ptr, const uint32_t *col, const double *val, uint32_t rows, const uint32_t *slice_base,
                       const uint32_t *slice_base16, double *sval, uint32_t *scol, short *scol16, hipStream_t st);
 
-unsigned sell_grid(uint32_t ngroups, int per_wg); // workgroups launched for ngroups 256-row groups
-unsigned vec_grid(uint32_t n);        // workgroups used by the element-wise kernels for length n
-void set_vec_grid_cap(unsigned cap);  // ranks sharing one GPU (tests): fewer workgroups per launch (0 = default)
-unsigned spmv_grid(uint32_t nlist);   // workgroups used by the CSR SpMV for nlist row blocks
 
 }  // namespace bicg

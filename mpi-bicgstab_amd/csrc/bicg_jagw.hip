@@ -20,10 +20,7 @@
 #include "bicg_device.h"
 #include "bicg_devfn.h"
 #include "bicg_reduce.h"
-
-#include <hip/hip_ext.h>
-#include <cstdio>
-#include <cstdlib>
+#include "bicg_launch.h"
 
 namespace bicg {
 
@@ -378,13 +375,7 @@ template <class K>
 static void jagd_go(K kernel, const SpmvArgs &a, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
 {
     const dim3 g(sell_grid(a.nlist, a.groups_per_wg)), b(kBlock);
-    if (e0 && e1) hipExtLaunchKernelGGL(kernel, g, b, 0, st, e0, e1, 0, a);
-    else hipLaunchKernelGGL(kernel, g, b, 0, st, a);
-    static const bool debug = getenv("BICG_DEBUG") != nullptr;
-    if (debug) {
-        const hipError_t err = hipGetLastError();
-        if (err != hipSuccess) fprintf(stderr, "bicgstab_hip: HIP error \"%s\" noticed at: k_spmv_jagd\n", hipGetErrorString(err));
-    }
+    launch_timed(kernel, g, b, st, e0, e1, a);
 }
 
 bool launch_spmv_jagd(const SpmvArgs &a, int ndot, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
@@ -428,13 +419,7 @@ static void jagw_go(K kernel, const SpmvArgs &a, hipStream_t st, hipEvent_t e0, 
 {
     const dim3 g(sell_grid(a.nlist, a.groups_per_wg)), b(kBlock);
     const unsigned lds = a.sell.win_slots * (unsigned)sizeof(double);
-    if (e0 && e1) hipExtLaunchKernelGGL(kernel, g, b, lds, st, e0, e1, 0, a);
-    else hipLaunchKernelGGL(kernel, g, b, lds, st, a);
-    static const bool debug = getenv("BICG_DEBUG") != nullptr;
-    if (debug) {
-        const hipError_t err = hipGetLastError();
-        if (err != hipSuccess) fprintf(stderr, "bicgstab_hip: HIP error \"%s\" noticed at: k_spmv_jagw\n", hipGetErrorString(err));
-    }
+    launch_timed_lds(kernel, g, b, lds, st, e0, e1, a);
 }
 
 bool launch_spmv_jagw(const SpmvArgs &a, int ndot, hipStream_t st, hipEvent_t e0, hipEvent_t e1)

@@ -7,7 +7,7 @@
 // (k_spmv_sell_epi, two launches of ~13 us on such a rank) pays a kernel boundary per SpMV; here an SpMV costs one
 // neighbour hand-off (~1-2 us) plus LDS arithmetic.
 //
-// Arithmetic: every expression is the one of FPipe1 / FPipe2 / sell_row (bicg_kernels.hip), operation for operation,
+// Arithmetic: every expression is the one of FPipe1 / FPipe2 (bicg_vec.hip) / sell_row (bicg_spmv_sell.h), operation for operation,
 // with -ffp-contract=off: rows and element-wise phases are bit-identical to the multi-launch path and to the
 // reference; the dot sums are associated differently (wavefront -> workgroup -> table in workgroup order), fixed, so
 // runs are bit-reproducible.
@@ -889,7 +889,7 @@ k_pipe_persist(PersistArgs a)
 
 
 // The pass over the other shifts' vectors of one row (reference src/shifted_solver.c:264-269, 296-299 / 806-807, 834-837;
-// FShiftUpdate / FShPipe2 of bicg_kernels.hip, operation for operation): p_j and x_j of the row are read once and written once
+// FShiftUpdate / FShPipe2 of bicg_vec.hip, operation for operation): p_j and x_j of the row are read once and written once
 // with the coefficients the helper published (L.coef). B shifts in flight per thread (2 B loads of 8 bytes). On a
 // latency-bound rank the two sets (2 x nsig x rows x 8 bytes: 51 MB for 16 shifts on 200 k rows) live in the Infinity Cache
 // between iterations -- ordinary loads and stores; non-temporal ones (set_nt) bypass it and are for sets that do not fit.

@@ -1,7 +1,7 @@
 // bicg_reduce.h -- device-side reductions and scalar recurrences shared by every translation unit that launches kernels
-// with dot products (bicg_kernels.hip, bicg_stencil.hip): the workgroup sum, the publication of a workgroup's partial sums
+// with dot products (bicg_spmv_*.hip, bicg_vec.hip, bicg_stencil.hip, ...): the workgroup sum, the publication of a workgroup's partial sums
 // (arrival tickets / tail finish / one partial per wavefront), the consumer-side finish of a dot group and the phases the
-// finishing thread applies. Moved here unchanged from bicg_kernels.hip (round 5) so that new kernels get a file of their own.
+// finishing thread applies. A header of its own since round 5, so that new kernels get a file of their own.
 #pragma once
 #include "bicg_device.h"
 #include "bicg_devfn.h"

@@ -1,7 +1,7 @@
 // bicg_spmm.hip -- Y_j = (A + sigma_j I) X_j for up to 16 vectors with the matrix read once (the per-shift verification loop of the
 // reference's shifted driver, src/test_shifted.c:129-154: BASELINE.json configs[4] "batched SpMV"), as a PIPELINE:
 // k_spmm_pipe. Padded slices with 16-bit column offsets whose distances fall into clusters (struct FusedWindow: banded and
-// stencil-like matrices, the Transport-shaped one among them); other layouts keep k_spmm_win / k_spmm_sell (bicg_kernels.hip).
+// stencil-like matrices, the Transport-shaped one among them); other layouts keep k_spmm_win / k_spmm_sell (bicg_spmm_sell.hip).
 //
 // What k_spmm_win did with its 311-316 us per 16 vectors (profiles/r06/spmm_notes.txt: the kernel with parts switched off, and its
 // counters): 135 us remained with no staging loads, no products and no row heads at all -- a workgroup's life was a chain of

@@ -4,7 +4,7 @@
 // generator numberings and of the FEM-like matrix. The reference multiplies A with many vectors in the verification loop of its
 // shifted driver, one product per shift (src/test_shifted.c:129-154: BASELINE.json configs[4] "batched SpMV").
 //
-// k_spmm_win (bicg_kernels.hip) walked these layouts as one workgroup per 256-row group, eight vectors per pass, every pass a chain
+// k_spmm_win (bicg_spmm_sell.hip) walked these layouts as one workgroup per 256-row group, eight vectors per pass, every pass a chain
 // of dependent trips (columns of the window -> 8 x values per slot -> LDS -> products, and one more trip per eight entries behind
 // a row's 16th) with two workgroups per CU to overlap them: 380 / 426 / 498 us for 16 vectors on the FEM-like matrix and the mesh in
 // generator / RCM order. Here (what each part cost before it was changed: profiles/r06/spmm_jag_notes.txt):

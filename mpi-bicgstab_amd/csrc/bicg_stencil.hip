@@ -1,7 +1,7 @@
 // bicg_stencil.hip -- the plane-marching product: y = A x for a block whose sliced-ELL plan found the 7-point stencil of a
 // grid in its lists (struct StencilDev, bicg_device.h; BASELINE.json configs[3], the 512^3 Laplacian of CA-BiCGStab).
 //
-// Why a kernel of its own: the slice-by-slice product of bicg_kernels.hip (k_spmv_sell, the loop over list-driven slices) moves
+// Why a kernel of its own: the slice-by-slice product of bicg_spmv_sell.h (k_spmv_sell, the loop over list-driven slices) moves
 // 2.3 GB per 512^3 product at the memory side but fills 5.4 GB into the vector L1s -- 20 cache lines per 64-row slice, every x
 // line fetched by five slices at five different times -- and is bound by those fills (one CU sustains ~10 B/cycle from its L1's
 // miss path: profiles/r04/laplace512_spmv_counters_lists_loop.txt). Here a wavefront keeps what it has fetched:
@@ -19,15 +19,12 @@
 // from the row (the "registers of the line below" ARE x[i - sy]); which entries a row has comes from the plan (StencilTab::bits
 // for the slice, StencilDev::cmask per row where rows of a slice differ), never from assumptions about grid faces.
 // The dot epilogue (NDOT) and its reduction are those of k_spmv_sell; EPI = 1 adds CA-BiCGStab's q = r - alpha s, y = w - alpha z,
-// (q,y), (y,y) (reference src/solver.c:225-232, FQY of bicg_kernels.hip, the same expressions) on the own rows behind z = A s:
+// (q,y), (y,y) (reference src/solver.c:225-232, FQY of bicg_vec.hip, the same expressions) on the own rows behind z = A s:
 // s_i is the register the product multiplied, z_i the sum it has just formed -- neither is read again.
 #include "bicg_device.h"
 #include "bicg_devfn.h"
 #include "bicg_reduce.h"
-
-#include <hip/hip_ext.h>
-#include <cstdio>
-#include <cstdlib>
+#include "bicg_launch.h"
 
 namespace bicg {
 
@@ -551,13 +548,7 @@ template <class K>
 static void stencil_go(K kernel, const SpmvArgs &a, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
 {
     const dim3 g(stencil_grid(a.sell.st)), b(kBlock);
-    if (e0 && e1) hipExtLaunchKernelGGL(kernel, g, b, 0, st, e0, e1, 0, a);
-    else hipLaunchKernelGGL(kernel, g, b, 0, st, a);
-    static const bool debug = getenv("BICG_DEBUG") != nullptr;
-    if (debug) {
-        const hipError_t err = hipGetLastError();
-        if (err != hipSuccess) fprintf(stderr, "bicgstab_hip: HIP error \"%s\" noticed at: k_spmv_stencil\n", hipGetErrorString(err));
-    }
+    launch_timed(kernel, g, b, st, e0, e1, a);
 }
 
 template <int R>

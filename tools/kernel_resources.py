@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Table of the compiler's per-kernel resource report (-Rpass-analysis=kernel-resource-usage output):
-   python tools/kernel_resources.py mpi-bicgstab_amd/build/kernel_resources_persist.txt [name filter]"""
+   python tools/kernel_resources.py mpi-bicgstab_amd/build/bicg_persist.res.txt [name filter]
+(one report per kernel unit, build/<unit>.res.txt; build/kernel_resources.txt holds all of them)"""
 import re, subprocess, sys
 txt = open(sys.argv[1]).read()
 flt = sys.argv[2] if len(sys.argv) > 2 else ""

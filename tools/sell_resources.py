@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """VGPRs / scratch / occupancy / SGPR spills of the single-GPU sliced-ELL products (no offd, no in-kernel exchange, ticket mode):
-   python tools/sell_resources.py [layouts, default 01]"""
+   python tools/sell_resources.py [layouts, default 01]
+(the layouts' units are bicg_spmv_sell_lay.hip compiled once per layout; read from build/kernel_resources.txt)"""
 import os, re, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 lay = sys.argv[1] if len(sys.argv) > 1 else "01"
