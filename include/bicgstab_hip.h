@@ -279,6 +279,28 @@ int bicg_shifted_residuals(bicg_ctx *ctx, const double *x_loc_set, const double 
 int bicg_spmm(bicg_ctx *ctx, const double *x_loc_set, const double *sigma, int nvec, double *y_loc_set, double *ms_device);
 /* per-iteration trace of the last run (record_trace): arrays of length >= iterations, may be NULL */
 int bicg_trace(bicg_ctx *ctx, double *alpha, double *omega, double *beta, double *dot_r);
+/* Plain BiCGStab (BICG_BICGSTAB) on nrhs independent systems A x_j = b_j that share the resident matrix: one SpMM per product
+ * for up to 16 columns, every column with its own alpha / omega / beta and its own convergence test.
+ * x_loc_set / r_loc_set are column-major, [j * local_rows + i], like x_loc_set of the shifted solvers: in = x0_j and b_j, out =
+ * the solution and the recursive residual of column j. Column j runs exactly the loop of reference src/solver.c:74-120 on
+ * (x0_j, b_j), with the loop condition dot_r > tol*tol*dot_zero && k < max_iter evaluated per column ON THE DEVICE at every
+ * iteration: a column whose condition has become false (a NaN in its scalars included) is frozen -- its x_j and r_j are not
+ * written again whatever the other columns go on doing --, and no column influences another. The dot products of a column are
+ * summed in an order that depends on local_rows only, so column j of any call is bit-identical to a one-column call on
+ * (x0_j, b_j). nrhs > 16 is processed as consecutive sets of 16 columns (the last one may be partial).
+ * opt->check_every iterations are enqueued between host reads of the columns' flags; opt->record_trace keeps alpha, omega, beta
+ * and (r,r) per column and iteration for bicg_multi_trace (max_iter x 16 x 4 doubles per set). res (nrhs entries, may be NULL):
+ * iterations, dot_r, dot_zero and breakdown_iteration of column j; the time fields of every entry are those of the whole call.
+ * Returns the largest k_j; -1 when the communicator has more than one rank (a per-column all-reduce is not built), -2 for a
+ * method other than BICG_BICGSTAB or nrhs < 1 -- a refused call touches nothing.
+ * The products are SpMMs that read P and R in place where bicg_spmm is available (BICG_FLAG_SPMM) and one bicg_spmv-style product
+ * per active column otherwise, or under BICG_PLAN="spmm=0" (read at the call). Memory: the first call allocates six sets of 16
+ * vectors beside the SpMM's own buffers -- 96 x 8 bytes per row, about 1.2 GB at 1.6 M rows --, released by bicg_destroy. */
+int bicg_solve_multi(bicg_ctx *ctx, int method, double *x_loc_set, double *r_loc_set, int nrhs,
+                     const bicg_options *opt, bicg_result *res /* nrhs entries, may be NULL */);
+/* trace of column `column` of the last bicg_solve_multi call run with record_trace: arrays of length >= that column's
+ * iterations, may be NULL. Returns 0; non-zero when nothing was recorded or the column is out of range. */
+int bicg_multi_trace(bicg_ctx *ctx, int column, double *alpha, double *omega, double *beta, double *dot_r);
 
 /* ---------------------------------------------------------------------------------------------
  * 4. Kernel-level entry points (parity tests, benchmarks).

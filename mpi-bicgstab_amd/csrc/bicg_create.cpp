@@ -1116,6 +1116,7 @@ void bicg_destroy(bicg_ctx *c)
                     c->wpart[0], c->wpart[1], c->shard_ll, c->tail_tab, c->tail_shard, c->hand_shard, c->alarm, c->mm_in, c->mm_xt, c->mm_yt, c->mm_part, c->mm_out, c->mm_sigma, c->ro_perm, c->ro_inv, c->ro_stage};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (void *p : c->persist_mem) if (p) (void)hipFree(p);
+    multi_release(c);
     release_p2p(c);
     if (c->push_dst0) (void)hipFree(c->push_dst0);
     if (c->push_stride) (void)hipFree(c->push_stride);

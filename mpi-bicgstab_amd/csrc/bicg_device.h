@@ -509,6 +509,27 @@ struct SpmmArgs {
 };
 
 
+// Multi-RHS plain BiCGStab (bicg_multi.hip, bicg_multi.cpp): one set of up to kSpmmCols independent recurrences on the resident
+// matrix. The six vector sets hold their columns `stride` apart; the scalars of every column live in one block per set.
+struct MultiVecs {
+    double *x, *r, *rh, *p, *s, *y;
+    size_t stride;
+    uint32_t n;
+};
+struct MultiScal {
+    double rTr[kSpmmCols], rTr_old[kSpmmCols], alpha[kSpmmCols], omega[kSpmmCols], beta[kSpmmCols];
+    double dot_r[kSpmmCols], dot_zero[kSpmmCols];
+    double tol2;
+    int max_iter;
+    int k[kSpmmCols];
+    int active[kSpmmCols];       // the column's loop condition (src/solver.c:86) still holds: 0 = frozen, nothing of it is written again
+    int breakdown[kSpmmCols];    // first iteration with a non-finite scalar (bicg_result.breakdown_iteration)
+    double *trace;               // [4][kSpmmCols][trace_cap]: alpha, omega, beta, (r,r) per column and iteration, or null
+    int trace_cap;
+};
+// the dot partials of a set: part[(slot * kSpmmCols + column) * nwg + workgroup], slot 0 / 1, nwg = multi_grid(n)
+enum MultiPhase { MP_INIT = 0, MP_ALPHA = 1, MP_OMEGA = 2, MP_END = 3 };
+
 // which product kernels have been launched since the last reset (bicg_product_kernels: tests and bench.py assert on the kernel
 // a matrix gets, not only on the plan's flags)
 enum ProductKernel : unsigned { PK_SELL_PAD = 1, PK_SELL_JAG = 2, PK_SELL_WINLOOP = 4, PK_JAGW = 8, PK_STENCIL = 16, PK_CSR = 32, PK_ROWS = 64,
@@ -563,6 +584,17 @@ hipError_t launch_spmm_pipe(const SpmmArgs &a, bool with_offd, hipStream_t st, h
 // the same pipeline on jagged slices with x windows (bicg_spmm_jag.hip, k_spmm_jpipe); hipErrorInvalidValue: the block does not qualify
 hipError_t launch_spmm_jpipe(const SpmmArgs &a, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 void preload_spmm_kernels();
+// bicg_multi.hip
+// the element-wise phases of a set of nv columns (grid: multi_grid(n) x nv; a frozen column's workgroups return at once) and the
+// finish of their dot partials (one workgroup per column: sums the column's partials in a fixed order, applies the recurrence)
+unsigned multi_grid(uint32_t n);
+void launch_multi_init(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st);     // r = b - s ; r# = r ; p = r ; (r,r)
+void launch_multi_dot_rs(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st);   // (r#,s)
+void launch_multi_q(const MultiVecs &v, int nv, MultiScal *S, hipStream_t st);                      // r -= alpha s
+void launch_multi_dot_qy(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st);   // (q,y), (y,y)
+void launch_multi_xr(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st);       // x, r updates ; (r,r), (r#,r)
+void launch_multi_p(const MultiVecs &v, int nv, MultiScal *S, hipStream_t st);                      // p = beta p + r - beta omega s
+void launch_multi_finish(int phase, int nv, MultiScal *S, const double *part, unsigned nwg, hipStream_t st);
 // bicg_persist.hip
 void preload_persist_kernels();
 // bicg_reorder.hip

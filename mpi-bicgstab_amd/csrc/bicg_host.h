@@ -2,6 +2,7 @@
 // device-memory helpers, section timing, and the prototypes of the functions that cross file boundaries.
 //   bicg_solver.cpp   dot groups, the distributed SpMV, the four iterations of reference src/solver.c, run_begin / iterate / end
 //   bicg_shifted.cpp  the shifted family (src/shifted_solver.c, src/shifted_switching_solver.c) and its section prints
+//   bicg_multi.cpp    bicg_solve_multi: plain BiCGStab on up to kSpmmCols right-hand sides per pass over the matrix
 //   bicg_create.cpp   bicg_create / bicg_create_device_csr: halo plan, upload of the diag block's plan (made by bicg_sell_plan.cpp,
 //                     host only: bicg_plan.h), slice descriptors, stencil plan, transport, persistent set-up, destroy
 //   bicg_dropin.cpp   the reference's own symbols (solver.h, shifted_solver.h, shifted_switching_solver.h), matrix residency
@@ -245,6 +246,15 @@ struct bicg_ctx {
     int  mm_win_env = 3;         // BICG_PLAN="spmm-window=0": the row-major kernel, 1: k_spmm_win everywhere, 3 (default): k_spmm_pipe where the block qualifies
     bool mm_dma = false;         // the last SpMM pass ran the pipelined kernel (bicg_spmm.hip)
 
+    // multi-RHS BiCGStab (bicg_solve_multi, bicg_multi.cpp): one set of kSpmmCols columns of X, R, R#, P, S, Y in one slab, the
+    // set's scalar block, its dot partials and its trace; allocated by the first call. The traces of the last call's sets are
+    // kept on the host for bicg_multi_trace: [column][4][mt_iters[column]]
+    double *mt_slab = nullptr, *mt_part = nullptr, *mt_trace = nullptr;
+    MultiScal *mt_S = nullptr;
+    int mt_trace_cap = 0;
+    std::vector<std::vector<double>> mt_host_trace;
+    std::vector<int> mt_iters;
+
     // BICG_PLAN="reorder=1|2" (DESIGN.md section 4.14b): the diag block was renumbered before it was planned. Everything on the device is
     // in the new numbering; the caller's vectors cross through perm / inv (vec_upload / vec_download below).
     int reorder_mode = 0;                // the token's value (ctx_read_switches)
@@ -413,7 +423,8 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
 void spmv_grp(bicg_ctx *c, double *xin, double *yout, int ndot = 0, const double *u = nullptr, int phase = PH_NONE);
 void spmv_epi(bicg_ctx *c, double *xin, double *yout, int epi, int nd, int phase);
 void halo_only(bicg_ctx *c, double *xin);
-void spmm_pass(bicg_ctx *c, int nvec, const double *sigma_host, bool with_b, bool sigma_staged = false, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+void spmm_pass(bicg_ctx *c, int nvec, const double *sigma_host, bool with_b, bool sigma_staged = false, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
+               double *in = nullptr, double *out = nullptr);
 void spmm_stage_sigma(bicg_ctx *c, int nvec, const double *sigma_host);
 bool spmm_possible(const bicg_ctx *c);
 void spmm_buffers(bicg_ctx *c);
@@ -426,6 +437,8 @@ int run_solver(bicg_ctx *c, int method, const bicg_options *opt_in, bicg_result 
 // ---- the shifted family (bicg_shifted.cpp)
 int run_shifted(bicg_ctx *c, int mode, double *x_set_host, double *r_host, const double *sigma, int nsig, int seed,
                 const bicg_options *opt_in, bicg_result *res);
+// ---- multi-RHS BiCGStab (bicg_multi.cpp)
+void multi_release(bicg_ctx *c);
 // ---- plan and context (bicg_create.cpp)
 bool all_ranks(Comm *comm, bool mine);
 void sell_order_for_big_grids(bicg_ctx *c, uint32_t ngroups);

@@ -1,0 +1,182 @@
+// bicg_multi.cpp -- bicg_solve_multi / bicg_multi_trace: plain BiCGStab (reference src/solver.c:74-120) on nrhs independent
+// systems that share the resident matrix, kSpmmCols columns per set, every product of a set ONE pass over the matrix (spmm_pass
+// reading P and R in place). Kernels: bicg_multi.hip. See bicg_host.h and DESIGN.md section 4.17.
+//
+// A set: X, R, R#, P, S, Y with kSpmmCols columns each, the columns c->stride apart (a multiple of 32 doubles: every column is
+// 256-byte aligned), one MultiScal block, the dot partials. Per iteration (each element-wise phase a launch over all columns of
+// the set, each finish one tiny launch with a workgroup per column):
+//   S = A P | (r#,s) | alpha | r -= alpha s | Y = A Q | (q,y), (y,y) | omega | x, r updates with (r,r), (r#,r) | beta, k, flag | p
+// The loop condition of a column is evaluated by the last finish ON THE DEVICE at every iteration; the workgroups of a column
+// whose condition is false return at once, so its x and r stay as they are. The host reads the flags every check_every iterations.
+#include "bicg_host.h"
+
+namespace {
+
+void multi_buffers(bicg_ctx *c)
+{
+    if (c->mt_slab) return;
+    const size_t st = c->stride;
+    // (+64: k_spmm_pipe copies 16-byte pairs, the last one may reach one column past a vector -- as for mm_in, spmm_buffers)
+    const size_t slab = 6 * (size_t)kSpmmCols * st + 64;
+    c->mt_slab = dev_alloc<double>(slab);
+    c->mt_part = dev_alloc<double>(2 * (size_t)kSpmmCols * multi_grid(c->n_loc));
+    c->mt_S = dev_alloc<MultiScal>(1);
+    BICG_HIP(hipMemset(c->mt_slab, 0, sizeof(double) * slab));      // padding rows and unused columns stay finite
+    BICG_HIP(hipDeviceSynchronize());      // the memset ran on the null stream: c->sc does not wait for it
+}
+
+MultiVecs multi_vecs(const bicg_ctx *c)
+{
+    const size_t set = (size_t)kSpmmCols * c->stride;
+    double *b = c->mt_slab;
+    return MultiVecs{b, b + set, b + 2 * set, b + 3 * set, b + 4 * set, b + 5 * set, c->stride, c->n_loc};
+}
+
+// out = A in for the nv columns of a set (`live`: the columns the host still knows to be active; a frozen column's product is
+// harmless and only the per-column form can skip it)
+void multi_product(bicg_ctx *c, bool spmm, double *in, double *out, int nv, const int *live)
+{
+    const size_t st = c->stride;
+    if (spmm) {
+        spmm_pass(c, nv, nullptr, false, true, nullptr, nullptr, in, out);
+        if (!c->mm_win) launch_vectors_from_rows(c->mm_yt, st, nv, c->n_loc, out, c->sc);      // the row-major form's second transpose
+        return;
+    }
+    for (int j = 0; j < nv; ++j)
+        if (live[j]) spmv(c, in + (size_t)j * st, out + (size_t)j * st, 0, nullptr, c->red(0, PH_NONE));
+}
+
+void fetch_multi(bicg_ctx *c, MultiScal *h)
+{
+    BICG_HIP(hipMemcpyAsync(h, c->mt_S, sizeof(MultiScal), hipMemcpyDeviceToHost, c->sc));
+    BICG_HIP(hipStreamSynchronize(c->sc));
+}
+
+}  // namespace
+
+void multi_release(bicg_ctx *c)
+{
+    for (void *p : {(void *)c->mt_slab, (void *)c->mt_part, (void *)c->mt_trace, (void *)c->mt_S})
+        if (p) (void)hipFree(p);
+    c->mt_slab = c->mt_part = c->mt_trace = nullptr; c->mt_S = nullptr;
+}
+
+extern "C" {
+
+int bicg_solve_multi(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_set, int nrhs, const bicg_options *opt_in,
+                     bicg_result *res)
+{
+    if (c->nranks > 1) return -1;
+    if (method != BICG_BICGSTAB || nrhs < 1) return -2;
+    use_device(c);
+    bicg_options o;
+    if (opt_in) o = *opt_in; else bicg_default_options(&o);
+    if (o.max_iter < 0) o.max_iter = 0;
+    if (o.check_every < 1) o.check_every = 1;
+    std::vector<double> ph_x, ph_r;        // a context without rows holds one phantom row: zeros in, nothing out (host_in)
+    if (c->phantom) { ph_x.assign((size_t)nrhs, 0.0); ph_r.assign((size_t)nrhs, 0.0); x_loc_set = ph_x.data(); r_loc_set = ph_r.data(); }
+
+    scal_reset(c);                         // the per-column products read the context's scalar block like bicg_spmv
+    c->time_kernels = false;
+    const bool spmm = c->spmm_ok && !plan_off("spmm");
+    if (spmm) spmm_buffers(c);
+    multi_buffers(c);
+    const bool tracing = o.record_trace != 0 && o.max_iter > 0;
+    if (tracing && c->mt_trace_cap < o.max_iter) {
+        if (c->mt_trace) BICG_HIP(hipFree(c->mt_trace));
+        c->mt_trace_cap = o.max_iter;
+        c->mt_trace = dev_alloc<double>(4 * (size_t)kSpmmCols * c->mt_trace_cap);
+    }
+    c->mt_host_trace.clear(); c->mt_iters.clear();
+    if (tracing) { c->mt_host_trace.resize((size_t)nrhs); c->mt_iters.assign((size_t)nrhs, 0); }
+
+    const MultiVecs v = multi_vecs(c);
+    const size_t n = c->n_loc;
+    const unsigned nwg = multi_grid(c->n_loc);
+    MultiScal h;
+    int kmax = 0;
+    double t_total = 0.0, t_iter = 0.0;
+    for (int j0 = 0; j0 < nrhs; j0 += kSpmmCols) {
+        const int nv = std::min(kSpmmCols, nrhs - j0);
+        memset(&h, 0, sizeof h);
+        h.tol2 = o.tol * o.tol;
+        h.max_iter = o.max_iter;
+        h.trace = tracing ? c->mt_trace : nullptr;
+        h.trace_cap = tracing ? c->mt_trace_cap : 0;
+        BICG_HIP(hipMemcpyAsync(c->mt_S, &h, sizeof h, hipMemcpyHostToDevice, c->sc));
+        vec_upload(c, v.x, c->stride, x_loc_set + (size_t)j0 * n, nv, true);
+        vec_upload(c, v.r, c->stride, r_loc_set + (size_t)j0 * n, nv, true);
+        BICG_HIP(hipStreamSynchronize(c->sc));      // (h is reused below; the uploads are not part of the timed span)
+
+        // ---- set-up phase (src/solver.c:74-83): s = A x ; r = b - s ; r# = r ; p = r ; (r,r)
+        const double t0 = now_sec();
+        int live[kSpmmCols];
+        for (int j = 0; j < kSpmmCols; ++j) live[j] = j < nv;
+        multi_product(c, spmm, v.x, v.s, nv, live);
+        launch_multi_init(v, nv, c->mt_S, c->mt_part, c->sc);
+        launch_multi_finish(MP_INIT, nv, c->mt_S, c->mt_part, nwg, c->sc);
+        fetch_multi(c, &h);
+        const double t1 = now_sec();
+
+        // ---- iterations (src/solver.c:86-120)
+        for (int it = 0; it < o.max_iter;) {
+            bool any = false;
+            for (int j = 0; j < nv; ++j) { live[j] = h.active[j]; any = any || live[j]; }
+            if (!any) break;
+            const int chunk = std::min(o.check_every, o.max_iter - it);
+            for (int i = 0; i < chunk; ++i) {
+                multi_product(c, spmm, v.p, v.s, nv, live);                              // s = A p
+                launch_multi_dot_rs(v, nv, c->mt_S, c->mt_part, c->sc);                  // (r#,s)
+                launch_multi_finish(MP_ALPHA, nv, c->mt_S, c->mt_part, nwg, c->sc);
+                launch_multi_q(v, nv, c->mt_S, c->sc);                                   // q = r - alpha s (kept in r)
+                multi_product(c, spmm, v.r, v.y, nv, live);                              // y = A q
+                launch_multi_dot_qy(v, nv, c->mt_S, c->mt_part, c->sc);                  // (q,y), (y,y)
+                launch_multi_finish(MP_OMEGA, nv, c->mt_S, c->mt_part, nwg, c->sc);
+                launch_multi_xr(v, nv, c->mt_S, c->mt_part, c->sc);                      // x, r ; (r,r), (r#,r)
+                launch_multi_finish(MP_END, nv, c->mt_S, c->mt_part, nwg, c->sc);
+                launch_multi_p(v, nv, c->mt_S, c->sc);                                   // p
+            }
+            it += chunk;
+            fetch_multi(c, &h);
+        }
+        const double t2 = now_sec();
+        t_total += t2 - t0; t_iter += t2 - t1;
+
+        vec_download(c, x_loc_set + (size_t)j0 * n, v.x, c->stride, nv, true);
+        vec_download(c, r_loc_set + (size_t)j0 * n, v.r, c->stride, nv, true);
+        BICG_HIP(hipStreamSynchronize(c->sc));
+        for (int j = 0; j < nv; ++j) {
+            kmax = std::max(kmax, h.k[j]);
+            if (res) {
+                bicg_result &q = res[j0 + j];
+                memset(&q, 0, sizeof q);
+                q.iterations = h.k[j]; q.dot_r = h.dot_r[j]; q.dot_zero = h.dot_zero[j]; q.breakdown_iteration = h.breakdown[j];
+            }
+            if (tracing) {
+                const int k = h.k[j];
+                std::vector<double> &t = c->mt_host_trace[(size_t)(j0 + j)];
+                t.resize(4 * (size_t)k);
+                c->mt_iters[(size_t)(j0 + j)] = k;
+                for (int q = 0; q < 4 && k > 0; ++q)
+                    BICG_HIP(hipMemcpy(t.data() + (size_t)q * k, c->mt_trace + ((size_t)q * kSpmmCols + j) * c->mt_trace_cap, sizeof(double) * k,
+                                       hipMemcpyDeviceToHost));
+            }
+        }
+    }
+    if (res)
+        for (int j = 0; j < nrhs; ++j) { res[j].seconds = t_total; res[j].iter_seconds = t_iter; }
+    return kmax;
+}
+
+int bicg_multi_trace(bicg_ctx *c, int column, double *alpha, double *omega, double *beta, double *dot_r)
+{
+    if (!c || column < 0 || (size_t)column >= c->mt_host_trace.size()) return 1;
+    const int k = c->mt_iters[(size_t)column];
+    const std::vector<double> &t = c->mt_host_trace[(size_t)column];
+    double *dst[4] = {alpha, omega, beta, dot_r};
+    for (int q = 0; q < 4; ++q)
+        if (dst[q] && k > 0) memcpy(dst[q], t.data() + (size_t)q * k, sizeof(double) * k);
+    return 0;
+}
+
+}  // extern "C"

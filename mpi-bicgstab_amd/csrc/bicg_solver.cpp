@@ -474,14 +474,19 @@ void spmm_stage_sigma(bicg_ctx *c, int nvec, const double *sigma_host)
 
 // e0 / e1 (optional): stamped at the start / end of the SpMM KERNEL where the launch can carry them (the windowed and the pipelined
 // form), else around the pass
-void spmm_pass(bicg_ctx *c, int nvec, const double *sigma_host, bool with_b, bool sigma_staged, hipEvent_t e0, hipEvent_t e1)
+// in / out (optional, bicg_multi.cpp): the shift-major input is read in place from `in` instead of c->mm_in, and the forms that
+// write shift-major (windowed, pipelined) write to `out` instead of c->mm_yt; the row-major form leaves its result in c->mm_yt
+void spmm_pass(bicg_ctx *c, int nvec, const double *sigma_host, bool with_b, bool sigma_staged, hipEvent_t e0, hipEvent_t e1,
+               double *in, double *out)
 {
     const size_t st = c->stride;
-    for (int j = 0; j < nvec; ++j) halo_only(c, c->mm_in + (size_t)j * st);
+    if (!in) in = c->mm_in;
+    if (!out) out = c->mm_yt;
+    for (int j = 0; j < nvec; ++j) halo_only(c, in + (size_t)j * st);
     // the windowed form (k_spmm_win) reads the shift-major vectors directly and writes Y shift-major into mm_yt
     const unsigned wslots = c->win_slots ? c->win_slots : (c->s_col16 && !c->sell_jag && c->fw.ncl > 0 ? c->fw.slots : 0u);
     c->mm_win = c->mm_win_env != 0 && spmm_win_vectors(wslots) > 0;
-    if (!c->mm_win) launch_rows_from_vectors(c->mm_in, st, nvec, c->n_loc + c->halo, c->mm_xt, c->sc);
+    if (!c->mm_win) launch_rows_from_vectors(in, st, nvec, c->n_loc + c->halo, c->mm_xt, c->sc);
     SpmmArgs a{};
     a.sell = {c->s_val, c->s_col, c->s_base, c->s_len, c->s_col16, c->s_base16, c->sell_jag ? 1 : 0, c->win_ptr, c->win_runs, c->win_slots, c->sell_perm};
     a.sell.win_list = c->win_list; a.sell.win_lptr = c->win_lptr; a.sell.win_ltotal = c->win_ltotal;
@@ -496,7 +501,7 @@ void spmm_pass(bicg_ctx *c, int nvec, const double *sigma_host, bool with_b, boo
     }
     c->mm_dma = false;
     if (c->mm_win) {
-        a.xs = c->mm_in; a.ys = with_b ? nullptr : c->mm_yt; a.vstride = st; a.nvec = nvec; a.wslots = wslots;
+        a.xs = in; a.ys = with_b ? nullptr : out; a.vstride = st; a.nvec = nvec; a.wslots = wslots;
         a.tail_most = c->jag_tail16_max;
         if (const char *sv = test_tok("spmm-skip")) a.dbg = atoi(sv);
         if (!c->win_slots) a.cl = c->fw;

@@ -63,6 +63,7 @@ EXPORTS = [
     "bicg_run_begin", "bicg_run_iterate", "bicg_run_iterate_timed", "bicg_run_end", "bicg_sync", "bicg_trace", "bicg_spmv", "bicg_dot", "bicg_spmv_bench", "bicg_plan_info", "bicg_ctx_flags", "bicg_spmm", "bicg_device_matrix_bytes", "bicg_uniform_entries", "bicg_constant_entries", "bicg_masked_rows", "bicg_stencil_info", "bicg_stencil_rows_per_lane", "bicg_comm_wait_stats", "bicg_plan_collisions", "bicg_product_kernels", "bicg_spmv_matrix_bytes", "bicg_last_shifted_persistent", "bicg_last_spmm_windowed", "bicg_dropin_context", "bicg_dropin_release", "bicg_dropin_stats",
     "bicg_mtx_load_block", "bicg_mtx_free", "bicg_partition", "bicg_halo_plan", "bicg_halo_send_counts", "bicg_halo_send_lists", "bicg_row_blocks", "bicg_window_plan", "bicg_window_slot", "bicg_version", "bicg_has_experiments", "bicg_switch_value", "bicg_switch_unknown", "bicg_stream_bench", "bicg_create_device_csr", "bicg_stencil7_device", "bicg_device_free", "bicg_persist_plan", "bicg_set_plan_threads", "bicg_sell_plan_digest",
     "bicg_reorder_plan", "bicg_permute_block", "bicg_reorder_info",
+    "bicg_solve_multi", "bicg_multi_trace",
 ]
 
 _lib = None
@@ -92,6 +93,10 @@ def lib():
         L.bicg_load.argtypes = [C.c_void_p, _dp, _dp]
         L.bicg_fetch.argtypes = [C.c_void_p, _dp, _dp]
         L.bicg_trace.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
+        L.bicg_solve_multi.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.POINTER(Options), C.POINTER(Result)]
+        L.bicg_solve_multi.restype = C.c_int
+        L.bicg_multi_trace.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
+        L.bicg_multi_trace.restype = C.c_int
         L.bicg_spmv.argtypes = [C.c_void_p, _dp, _dp]
         L.bicg_dot.argtypes = [C.c_void_p, _dp, _dp]
         L.bicg_dot.restype = C.c_double
@@ -327,6 +332,31 @@ class Context:
         res = Result()
         k = lib().bicg_solve(self.h, METHODS[method], _d(x), _d(r), C.byref(o), C.byref(res))
         return dict(k=k, x=x, r=r, dot_r=res.dot_r, dot_zero=res.dot_zero, result=res)
+
+    def solve_multi(self, B, X0=None, method: str = "bicgstab", **kw):
+        """Plain BiCGStab on the rows of B [nrhs][n] as independent right-hand sides of the resident matrix, 16 columns per pass
+        over the matrix (bicg_solve_multi): dict(k [nrhs] int array, x [nrhs][n], r [nrhs][n], results [nrhs] of Result, rc = the
+        call's return value: the largest k, or the negative code of a refused call -- x and r are then X0 and B)."""
+        r = np.array(B, dtype=np.float64).reshape(-1, self.n)
+        nrhs = r.shape[0]
+        x = np.zeros((nrhs, self.n)) if X0 is None else np.array(X0, dtype=np.float64).reshape(nrhs, self.n)
+        kw.setdefault("quiet", 1)
+        o = self.options(**kw)
+        res = (Result * max(nrhs, 1))()
+        rc = lib().bicg_solve_multi(self.h, METHODS[method], _d(x), _d(r), nrhs, C.byref(o), res)
+        results = list(res)[:nrhs] if rc >= 0 else []
+        self._multi_k = [q.iterations for q in results]
+        return dict(k=np.array(self._multi_k, dtype=np.int64), x=x, r=r, results=results, rc=rc)
+
+    def multi_trace(self, column: int, k: int):
+        """trace of one column of the last solve_multi(record_trace=1): the dict of trace(); None when nothing was recorded"""
+        done = getattr(self, "_multi_k", [])
+        if not 0 <= column < len(done):
+            return None
+        arrs = [np.zeros(max(k, done[column], 1)) for _ in range(4)]      # the library writes the column's whole trace
+        if lib().bicg_multi_trace(self.h, column, *[_d(a) for a in arrs]) != 0:
+            return None
+        return dict(zip(("alpha", "omega", "beta", "dotr"), [a[:min(k, done[column])] for a in arrs]))
 
     SHIFTED = {"shifted_lopbicgstab": 0, "shifted_pipe_lopbicgstab": 1, "shifted_bicgstab": 2,
                "shifted_lopbicg": 3, "shifted_lopbicg_switching": 4}
