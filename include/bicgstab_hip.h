@@ -291,11 +291,24 @@ int bicg_trace(bicg_ctx *ctx, double *alpha, double *omega, double *beta, double
  * opt->check_every iterations are enqueued between host reads of the columns' flags; opt->record_trace keeps alpha, omega, beta
  * and (r,r) per column and iteration for bicg_multi_trace (max_iter x 16 x 4 doubles per set). res (nrhs entries, may be NULL):
  * iterations, dot_r, dot_zero and breakdown_iteration of column j; the time fields of every entry are those of the whole call.
- * Returns the largest k_j; -1 when the communicator has more than one rank (a per-column all-reduce is not built), -2 for a
- * method other than BICG_BICGSTAB or nrhs < 1 -- a refused call touches nothing.
+ * Returns the largest k_j; -2 for a method other than BICG_BICGSTAB or nrhs < 1 -- a refused call touches nothing.
  * The products are SpMMs that read P and R in place where bicg_spmm is available (BICG_FLAG_SPMM) and one bicg_spmv-style product
  * per active column otherwise, or under BICG_PLAN="spmm=0" (read at the call). Memory: the first call allocates six sets of 16
- * vectors beside the SpMM's own buffers -- 96 x 8 bytes per row, about 1.2 GB at 1.6 M rows --, released by bicg_destroy. */
+ * vectors beside the SpMM's own buffers -- 96 x 8 bytes per row, about 1.2 GB at 1.6 M rows --, released by bicg_destroy.
+ * COLLECTIVE when the communicator has more than one rank: every rank calls with the same method, nrhs, max_iter, check_every
+ * and tol (ranks without rows pass nrhs and empty arrays). The call begins with a check of exactly that, one all-reduce in which
+ * every rank takes part whatever its own arguments are: -1 means the ranks did NOT pass the same arguments (or do not agree on
+ * BICG_PLAN="spmm=0") -- every rank returns -1 and nothing is touched; when they agree and the arguments are refusable every rank
+ * returns -2. Per product a set costs ONE halo exchange (the 16 halos packed peer-major; BICG_PLAN="halo-set=0", read at the
+ * call, or a peer-to-peer context: one per column), per dot group ONE all-reduce of nranks x 32 doubles that gathers every
+ * rank's local sums -- each rank's row is added to zeros only, which is exact --, after which every rank adds the rows in the same
+ * fixed order (the association of a recursive-doubling all-reduce, ascending rank order up to three ranks).
+ * What is bit-identical to what, across ranks: (a) k, dot_r, dot_zero, breakdown_iteration and the trace of a column are the same bytes on every rank, so all ranks take the same decisions; (b) column j of any call is bit-identical to a one-column
+ * collective call on (x0_j, b_j) at the same partition, whatever check_every is; (c) the result does not depend on the
+ * transport's summation order, on halo-set, or on spmm=0. It is NOT bit-identical to the one-rank call: the partition decides
+ * how a column's dot sums are associated (as it does for the reference under MPI). One rank: unchanged.
+ * On a peer-to-peer context (bicg_comm_enable_p2p) the products use the peer-to-peer halo path, one exchange per column, while
+ * the all-reduces of the dot groups go through the transport underneath: correct, not optimised. */
 int bicg_solve_multi(bicg_ctx *ctx, int method, double *x_loc_set, double *r_loc_set, int nrhs,
                      const bicg_options *opt, bicg_result *res /* nrhs entries, may be NULL */);
 /* trace of column `column` of the last bicg_solve_multi call run with record_trace: arrays of length >= that column's
@@ -320,6 +333,12 @@ int bicg_stream_bench(int kind, unsigned long long bytes_per_array, int reps, do
 /* 1 after a peer-to-peer wait of this context timed out (only reachable with BICG_P2P_SOFT_FAIL=1; the
  * default is to print the error and exit like any other HIP/RCCL failure). The solve in progress stops. */
 int bicg_comm_failed(bicg_ctx *ctx);
+/* Transport collectives issued for this context since bicg_create: out = {halo exchanges (the transport's exchange of device
+ * buffers: one per bicg_spmv-style product, one per SET of vectors in bicg_spmm / bicg_shifted_residuals / bicg_solve_multi),
+ * all-reduces (one per dot group; one per dot group of a whole set in bicg_solve_multi)}. Host counters, incremented where the
+ * calls are made: exchanges and sums that travel on the peer-to-peer data path are not transport calls and are not counted, and
+ * a rank with neither halo nor send list issues no exchange. Returns 0. */
+int bicg_comm_counts(bicg_ctx *ctx, unsigned long long out[2]);
 /* How long the exchanges of the last solve made the persistent kernels wait (multi-rank, peer-to-peer data path): one sample per
  * exchange, taken on the device clock inside the launch. out = {all-reduce of a dot group through the mailboxes: p50, p99; a
  * boundary workgroup's wait from publishing its own values to a complete window, the neighbour's halo values included: p50, p99

@@ -250,6 +250,12 @@ int bicg_spmv_bench(bicg_ctx *c, int reps, double *ms_per_spmv)
 
 int bicg_comm_failed(bicg_ctx *c) { return c->comm_failed ? 1 : 0; }
 
+int bicg_comm_counts(bicg_ctx *c, unsigned long long out[2])
+{
+    out[0] = c->n_exchange; out[1] = c->n_allreduce;
+    return 0;
+}
+
 int bicg_section_times(bicg_ctx *c, double ms[4], int *iterations, int *marks)
 {
     if (!c) return 1;

@@ -60,7 +60,7 @@ struct HostComm : Comm {
     bicg_allreduce_fn ar = nullptr;
     bicg_alltoallv_fn a2a = nullptr;
     void *user = nullptr;
-    std::vector<double> hs, hr;
+    std::vector<double> hs, hr, wide;
     std::vector<int> bs_cnt, bs_dsp, br_cnt, br_dsp;
 
     const char *name() const override { return "host"; }
@@ -68,8 +68,9 @@ struct HostComm : Comm {
 
     void allreduce_sum(double *dev, int n, hipStream_t st) override
     {
-        double tmp[64];
-        if (n > 64) die("allreduce_sum", "group too wide");
+        double small[64];
+        double *tmp = small;
+        if (n > 64) { wide.resize((size_t)n); tmp = wide.data(); }      // (the gathered sums of a multi-RHS set: nranks x 32 doubles)
         BICG_HIP(hipMemcpyAsync(tmp, dev, sizeof(double) * n, hipMemcpyDeviceToHost, st));
         BICG_HIP(hipStreamSynchronize(st));
         ar(tmp, n, user);

@@ -1113,7 +1113,7 @@ void bicg_destroy(bicg_ctx *c)
     (void)hipDeviceSynchronize();
     void *ptrs[] = {c->d_val, c->d_col, c->d_ptr, c->o_val, c->o_col, c->o_ptr, c->desc_int, c->desc_bnd, c->s_val, c->s_col, c->s_base, c->s_len, c->s_col16, c->s_base16, c->s_ubase, c->s_uoff, c->s_vbase, c->s_uval, c->s_mbase, c->s_rmask, c->s_desc, c->s_uoff8, c->st_code, c->st_tab, c->st_cmask, c->st_wbits, c->d_col16, c->win_ptr, c->win_runs, c->win_list, c->win_lptr, c->win_ltotal, c->sell_perm, c->lane_info, c->waitlog, c->sh_dev, c->sh_arrays, c->p_set, c->x_set, c->glist_int, c->glist_bnd,
                     c->send_idx, c->sendbuf, c->slab, c->partial, c->shard_tot, c->counter, c->Sbuf, c->trace, c->sw_buf,
-                    c->wpart[0], c->wpart[1], c->shard_ll, c->tail_tab, c->tail_shard, c->hand_shard, c->alarm, c->mm_in, c->mm_xt, c->mm_yt, c->mm_part, c->mm_out, c->mm_sigma, c->ro_perm, c->ro_inv, c->ro_stage};
+                    c->wpart[0], c->wpart[1], c->shard_ll, c->tail_tab, c->tail_shard, c->hand_shard, c->alarm, c->mm_in, c->mm_xt, c->mm_yt, c->mm_part, c->mm_out, c->mm_sigma, c->set_send, c->set_recv, c->set_smap, c->set_rmap, c->ro_perm, c->ro_inv, c->ro_stage};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (void *p : c->persist_mem) if (p) (void)hipFree(p);
     multi_release(c);

@@ -595,6 +595,10 @@ void launch_multi_dot_qy(const MultiVecs &v, int nv, MultiScal *S, double *part,
 void launch_multi_xr(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st);       // x, r updates ; (r,r), (r#,r)
 void launch_multi_p(const MultiVecs &v, int nv, MultiScal *S, hipStream_t st);                      // p = beta p + r - beta omega s
 void launch_multi_finish(int phase, int nv, MultiScal *S, const double *part, unsigned nwg, hipStream_t st);
+// the finish across ranks: this rank's sums of all kSpmmCols columns into its row of red[nranks][2][kSpmmCols] (the other rows
+// zeroed), and -- after the all-reduce of red -- the rows added in a fixed order (rank_tree_sum's) and the recurrence applied, one thread per column
+void launch_multi_sum(int phase, int nv, const MultiScal *S, const double *part, unsigned nwg, double *red, int nranks, int rank, hipStream_t st);
+void launch_multi_apply(int phase, int nv, MultiScal *S, double *red, int nranks, hipStream_t st);
 // bicg_persist.hip
 void preload_persist_kernels();
 // bicg_reorder.hip
@@ -605,6 +609,12 @@ void launch_permute_out(const double *src, size_t src_stride, double *dst, size_
 // bicg_exchange.hip
 void launch_apply(Scal *S, int phase, hipStream_t st);
 void launch_halo_pack(const double *x, const uint32_t *send_idx, uint32_t nsend, double *sendbuf, Scal *S, hipStream_t st);
+// the halo exchange of a SET of nvec vectors `stride` apart (spmm_pass): map[i] = {first entry, entries} of the peer that entry i
+// of the send list / of the halo belongs to; peer p's block of a buffer starts at nvec * first and holds vector j at + j * entries
+void launch_halo_pack_set(const double *x, size_t stride, int nvec, const uint32_t *send_idx, const uint2 *map, uint32_t nsend, double *sendbuf,
+                          const Scal *S, hipStream_t st);
+void launch_halo_unpack_set(const double *recvbuf, const uint2 *map, uint32_t halo, int nvec, double *tail, size_t stride, const Scal *S,
+                            hipStream_t st);
 // peer-to-peer transport: wait for the P contributions of group pr.seq, sum n values, apply `phase`
 void launch_apply_p2p(Scal *S, int phase, int n, const P2pRed &pr, unsigned long long timeout_ticks, hipStream_t st);
 // halo exchange: entry i of the send list goes to dst0[i] + (seq % kHaloRing) * dst_stride[i] bytes

@@ -79,6 +79,53 @@ void launch_halo_pack(const double *x, const uint32_t *send_idx, uint32_t nsend,
     BICG_LAUNCH(k_halo_pack, dim3(g), dim3(kBlock), 0, st, x, send_idx, nsend, sendbuf, S);
 }
 
+// The same for the nvec vectors of a set (blockIdx.y: the vector), into ONE send buffer laid out peer-major: what goes to peer p
+// is one contiguous block (nvec * scnt[p] doubles from nvec * sdsp[p]) with vector j at + j * scnt[p], so a single transport
+// exchange with counts and displacements scaled by nvec carries the set. map[i] = {sdsp[p], scnt[p]} of entry i's peer.
+__global__ void __launch_bounds__(kBlock) k_halo_pack_set(const double *x, size_t stride, const uint32_t *idx, const uint2 *map, uint32_t n,
+                                                          double *out, const Scal *S)
+{
+    if (S->done) return;
+    const uint32_t j = blockIdx.y, nvec = gridDim.y;
+    const double *xj = x + (size_t)j * stride;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+        const uint2 m = map[i];
+        out[(size_t)nvec * m.x + (size_t)j * m.y + (i - m.x)] = xj[idx[i]];
+    }
+}
+
+void launch_halo_pack_set(const double *x, size_t stride, int nvec, const uint32_t *send_idx, const uint2 *map, uint32_t nsend, double *sendbuf,
+                          const Scal *S, hipStream_t st)
+{
+    if (nsend == 0 || nvec < 1) return;
+    unsigned g = (nsend + kBlock - 1) / kBlock;
+    if (g > 1024) g = 1024;
+    BICG_LAUNCH(k_halo_pack_set, dim3(g, (unsigned)nvec), dim3(kBlock), 0, st, x, stride, send_idx, map, nsend, sendbuf, S);
+}
+
+// ... and the landing buffer (same layout, map[i] = {rdsp[p], rcnt[p]} of halo entry i's owner) scattered into the halo tails of
+// the vectors: tail + j * stride + i, i < halo -- inside vector j's own stride, the slack behind the last vector stays untouched
+__global__ void __launch_bounds__(kBlock) k_halo_unpack_set(const double *in, const uint2 *map, uint32_t n, double *tail, size_t stride,
+                                                            const Scal *S)
+{
+    if (S->done) return;
+    const uint32_t j = blockIdx.y, nvec = gridDim.y;
+    double *tj = tail + (size_t)j * stride;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+        const uint2 m = map[i];
+        tj[i] = in[(size_t)nvec * m.x + (size_t)j * m.y + (i - m.x)];
+    }
+}
+
+void launch_halo_unpack_set(const double *recvbuf, const uint2 *map, uint32_t halo, int nvec, double *tail, size_t stride, const Scal *S,
+                            hipStream_t st)
+{
+    if (halo == 0 || nvec < 1) return;
+    unsigned g = (halo + kBlock - 1) / kBlock;
+    if (g > 1024) g = 1024;
+    BICG_LAUNCH(k_halo_unpack_set, dim3(g, (unsigned)nvec), dim3(kBlock), 0, st, recvbuf, map, halo, tail, stride, S);
+}
+
 void launch_apply_p2p(Scal *S, int phase, int n, const P2pRed &pr, unsigned long long timeout_ticks, hipStream_t st)
 {
     BICG_LAUNCH(k_apply_p2p, dim3(1), dim3(kBlock), 0, st, S, phase, n, pr, timeout_ticks);

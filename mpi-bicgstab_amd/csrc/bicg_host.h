@@ -135,6 +135,13 @@ struct bicg_ctx {
     uint32_t nsend = 0;
     uint32_t *send_idx = nullptr;
     double *sendbuf = nullptr;
+    // the exchange of a SET of vectors (spmm_pass, halo_set): kSpmmCols x nsend / kSpmmCols x halo doubles laid out peer-major, and
+    // per entry of the send list / of the halo {first entry, entries} of its peer (k_halo_pack_set); made with the SpMM buffers
+    double *set_send = nullptr, *set_recv = nullptr;
+    uint2 *set_smap = nullptr, *set_rmap = nullptr;
+    std::vector<int> set_cnt[4];           // scnt, sdsp, rcnt, rdsp of the current set: the context's times its vectors
+    // transport calls issued for this context since bicg_create (bicg_comm_counts): Comm::exchange, Comm::allreduce_sum
+    unsigned long long n_exchange = 0, n_allreduce = 0;
     // peer-to-peer transport (comm->p2p): landing ring for incoming halo values and, per entry of
     // the send list, where it goes in the ring of the rank that needs it
     P2p *p2p = nullptr;
@@ -251,6 +258,7 @@ struct bicg_ctx {
     // kept on the host for bicg_multi_trace: [column][4][mt_iters[column]]
     double *mt_slab = nullptr, *mt_part = nullptr, *mt_trace = nullptr;
     MultiScal *mt_S = nullptr;
+    double *mt_red = nullptr;              // [nranks][2][kSpmmCols]: every rank's local dot sums, gathered by one all-reduce (k_multi_sum)
     int mt_trace_cap = 0;
     std::vector<std::vector<double>> mt_host_trace;
     std::vector<int> mt_iters;
@@ -380,6 +388,19 @@ inline void vec_download(bicg_ctx *c, double *host, const double *dev, size_t de
     }
 }
 
+// every transport collective of a context goes through these two: they count (bicg_comm_counts)
+inline void ctx_allreduce(bicg_ctx *c, double *dev, int n, hipStream_t st)
+{
+    c->n_allreduce++;
+    c->comm->allreduce_sum(dev, n, st);
+}
+inline void ctx_exchange(bicg_ctx *c, const double *send, const int *scnt, const int *sdsp, double *recv, const int *rcnt, const int *rdsp,
+                         hipStream_t st)
+{
+    c->n_exchange++;
+    c->comm->exchange(send, scnt, sdsp, recv, rcnt, rdsp, st);
+}
+
 inline void use_device(const bicg_ctx *c)
 {
     if (!c->comm)
@@ -423,6 +444,7 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
 void spmv_grp(bicg_ctx *c, double *xin, double *yout, int ndot = 0, const double *u = nullptr, int phase = PH_NONE);
 void spmv_epi(bicg_ctx *c, double *xin, double *yout, int epi, int nd, int phase);
 void halo_only(bicg_ctx *c, double *xin);
+void halo_set(bicg_ctx *c, double *in, int nvec);      // ... of nvec vectors c->stride apart in ONE transport exchange
 void spmm_pass(bicg_ctx *c, int nvec, const double *sigma_host, bool with_b, bool sigma_staged = false, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
                double *in = nullptr, double *out = nullptr);
 void spmm_stage_sigma(bicg_ctx *c, int nvec, const double *sigma_host);

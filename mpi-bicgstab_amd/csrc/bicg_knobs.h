@@ -62,7 +62,7 @@ inline bool knob_value_ok(const char *name, size_t name_len, const char *v, size
 inline const char *const *knob_names(const char *set)
 {
     static const char *const plan[] = {"stencil", "lines", "planes", "ca-fuse", "layout", "window", "col16", "uniform", "constant", "masked",
-                                       "desc", "lists", "jagw", "spmm", "spmm-window", "fuse-pipe", "pipe-probe", "halo-fused", "window-list", "wide", "reorder", "handover", nullptr};
+                                       "desc", "lists", "jagw", "spmm", "spmm-window", "fuse-pipe", "pipe-probe", "halo-fused", "window-list", "wide", "reorder", "handover", "halo-set", nullptr};
     static const char *const persist[] = {"0", "off", "chunk", "shifted", nullptr};      // (the persistent forms are the default: there is no "on")
     static const char *const test[] = {"force-comm", "spin-ticks", "p2p-fault-after", "plan-collide", "spmm-skip", "spmm-gstep", "spmm-tile", "spmm-jres", nullptr};
     static const char *const none[] = {nullptr};

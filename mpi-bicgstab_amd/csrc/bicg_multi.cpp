@@ -8,6 +8,13 @@
 //   S = A P | (r#,s) | alpha | r -= alpha s | Y = A Q | (q,y), (y,y) | omega | x, r updates with (r,r), (r#,r) | beta, k, flag | p
 // The loop condition of a column is evaluated by the last finish ON THE DEVICE at every iteration; the workgroups of a column
 // whose condition is false return at once, so its x and r stay as they are. The host reads the flags every check_every iterations.
+//
+// Across ranks (nranks > 1) the call is collective. Every product of a set is one spmm_pass -- ONE halo exchange for the set
+// (halo_set) -- or, without the SpMM, one collective spmv() per column the agreed flags show as live. Every finish is k_multi_sum,
+// ONE all-reduce of mt_red[nranks][2][kSpmmCols] that gathers the ranks' local sums (each rank's row is added to zeros only), and
+// k_multi_apply, which adds the rows in a fixed order: the scalars, hence the flags the host reads, are the same bytes on every rank,
+// so the ranks cannot disagree about the next collective. On a peer-to-peer context the products use its data path (halo_only /
+// spmv) while these all-reduces go through the transport underneath (c->comm->allreduce_sum): correct, not optimised.
 #include "bicg_host.h"
 
 namespace {
@@ -49,16 +56,56 @@ void multi_product(bicg_ctx *c, bool spmm, double *in, double *out, int nv, cons
 void fetch_multi(bicg_ctx *c, MultiScal *h)
 {
     BICG_HIP(hipMemcpyAsync(h, c->mt_S, sizeof(MultiScal), hipMemcpyDeviceToHost, c->sc));
+    if (c->p2p) fetch_scal(c);      // synchronises, and reports a peer that never delivered its halo values
+    else BICG_HIP(hipStreamSynchronize(c->sc));
+}
+
+constexpr int kRedRow = 2 * kSpmmCols;      // doubles per rank in mt_red
+
+void multi_red_buffer(bicg_ctx *c)
+{
+    if (!c->mt_red) c->mt_red = dev_alloc<double>((size_t)c->nranks * kRedRow);
+}
+
+// the dot group `phase` of a set: one rank -> k_multi_finish; several -> local sums, one gathering all-reduce, apply
+void multi_finish(bicg_ctx *c, int phase, int nv, unsigned nwg)
+{
+    if (c->nranks == 1) { launch_multi_finish(phase, nv, c->mt_S, c->mt_part, nwg, c->sc); return; }
+    launch_multi_sum(phase, nv, c->mt_S, c->mt_part, nwg, c->mt_red, c->nranks, c->rank, c->sc);
+    ctx_allreduce(c, c->mt_red, c->nranks * kRedRow, c->sc);
+    launch_multi_apply(phase, nv, c->mt_S, c->mt_red, c->nranks, c->sc);
+}
+
+// Collective: did every rank pass the same arguments? Each rank writes what the sequence of collectives depends on into its row
+// of the gather buffer (every value an integer a double holds exactly; tol as the two halves of its bit pattern), one all-reduce
+// gathers the rows, every rank compares them all -- so every rank reaches the same verdict.
+bool multi_agree(bicg_ctx *c, int method, int nrhs, const bicg_options &o, bool spmm)
+{
+    const int P = c->nranks;
+    unsigned long long tb = 0;
+    static_assert(sizeof tb == sizeof o.tol, "tol is a double");
+    memcpy(&tb, &o.tol, sizeof tb);
+    const double mine[7] = {(double)nrhs, (double)method, (double)o.max_iter, (double)o.check_every, (double)(tb & 0xffffffffull),
+                            (double)(tb >> 32), spmm ? 1.0 : 0.0};
+    std::vector<double> all((size_t)P * kRedRow, 0.0);
+    std::copy(mine, mine + 7, all.begin() + (size_t)c->rank * kRedRow);
+    BICG_HIP(hipMemcpyAsync(c->mt_red, all.data(), sizeof(double) * all.size(), hipMemcpyHostToDevice, c->sc));
+    BICG_HIP(hipStreamSynchronize(c->sc));      // (all is pageable: the copy has left it before the transport may touch the stream)
+    ctx_allreduce(c, c->mt_red, P * kRedRow, c->sc);
+    BICG_HIP(hipMemcpyAsync(all.data(), c->mt_red, sizeof(double) * all.size(), hipMemcpyDeviceToHost, c->sc));
     BICG_HIP(hipStreamSynchronize(c->sc));
+    for (int p = 0; p < P; ++p)
+        if (memcmp(all.data() + (size_t)p * kRedRow, mine, sizeof mine) != 0) return false;
+    return true;
 }
 
 }  // namespace
 
 void multi_release(bicg_ctx *c)
 {
-    for (void *p : {(void *)c->mt_slab, (void *)c->mt_part, (void *)c->mt_trace, (void *)c->mt_S})
+    for (void *p : {(void *)c->mt_slab, (void *)c->mt_part, (void *)c->mt_trace, (void *)c->mt_S, (void *)c->mt_red})
         if (p) (void)hipFree(p);
-    c->mt_slab = c->mt_part = c->mt_trace = nullptr; c->mt_S = nullptr;
+    c->mt_slab = c->mt_part = c->mt_trace = c->mt_red = nullptr; c->mt_S = nullptr;
 }
 
 extern "C" {
@@ -66,13 +113,18 @@ extern "C" {
 int bicg_solve_multi(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_set, int nrhs, const bicg_options *opt_in,
                      bicg_result *res)
 {
-    if (c->nranks > 1) return -1;
-    if (method != BICG_BICGSTAB || nrhs < 1) return -2;
-    use_device(c);
     bicg_options o;
     if (opt_in) o = *opt_in; else bicg_default_options(&o);
     if (o.max_iter < 0) o.max_iter = 0;
     if (o.check_every < 1) o.check_every = 1;
+    if (c->nranks > 1) {
+        // collective from here on: a rank whose own arguments are refusable still takes part in the check, or the others would wait
+        use_device(c);
+        multi_red_buffer(c);
+        if (!multi_agree(c, method, nrhs, o, c->spmm_ok && !plan_off("spmm"))) return -1;
+    }
+    if (method != BICG_BICGSTAB || nrhs < 1) return -2;
+    use_device(c);
     std::vector<double> ph_x, ph_r;        // a context without rows holds one phantom row: zeros in, nothing out (host_in)
     if (c->phantom) { ph_x.assign((size_t)nrhs, 0.0); ph_r.assign((size_t)nrhs, 0.0); x_loc_set = ph_x.data(); r_loc_set = ph_r.data(); }
 
@@ -114,7 +166,7 @@ int bicg_solve_multi(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_s
         for (int j = 0; j < kSpmmCols; ++j) live[j] = j < nv;
         multi_product(c, spmm, v.x, v.s, nv, live);
         launch_multi_init(v, nv, c->mt_S, c->mt_part, c->sc);
-        launch_multi_finish(MP_INIT, nv, c->mt_S, c->mt_part, nwg, c->sc);
+        multi_finish(c, MP_INIT, nv, nwg);
         fetch_multi(c, &h);
         const double t1 = now_sec();
 
@@ -127,13 +179,13 @@ int bicg_solve_multi(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_s
             for (int i = 0; i < chunk; ++i) {
                 multi_product(c, spmm, v.p, v.s, nv, live);                              // s = A p
                 launch_multi_dot_rs(v, nv, c->mt_S, c->mt_part, c->sc);                  // (r#,s)
-                launch_multi_finish(MP_ALPHA, nv, c->mt_S, c->mt_part, nwg, c->sc);
+                multi_finish(c, MP_ALPHA, nv, nwg);
                 launch_multi_q(v, nv, c->mt_S, c->sc);                                   // q = r - alpha s (kept in r)
                 multi_product(c, spmm, v.r, v.y, nv, live);                              // y = A q
                 launch_multi_dot_qy(v, nv, c->mt_S, c->mt_part, c->sc);                  // (q,y), (y,y)
-                launch_multi_finish(MP_OMEGA, nv, c->mt_S, c->mt_part, nwg, c->sc);
+                multi_finish(c, MP_OMEGA, nv, nwg);
                 launch_multi_xr(v, nv, c->mt_S, c->mt_part, c->sc);                      // x, r ; (r,r), (r#,r)
-                launch_multi_finish(MP_END, nv, c->mt_S, c->mt_part, nwg, c->sc);
+                multi_finish(c, MP_END, nv, nwg);
                 launch_multi_p(v, nv, c->mt_S, c->sc);                                   // p
             }
             it += chunk;

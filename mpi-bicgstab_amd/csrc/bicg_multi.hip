@@ -11,6 +11,7 @@
 //                       sums are folded by a fixed tree in LDS, thread 0 applies the recurrence to the column's scalars.
 //                       No atomics, no tickets: the order of a column's sums depends neither on the number of columns nor on
 //                       the column's place in the set.
+//   k_multi_sum<PH>, k_multi_apply<PH>  the finish across ranks, split around one all-reduce that acts as an all-gather (below).
 //
 // Compiled with -ffp-contract=off like every unit: each daxpy / dscal of the reference stays a rounding of its own.
 #include "bicg_device.h"
@@ -177,16 +178,9 @@ static __device__ __forceinline__ double column_sum(const double *part, int d, i
     return sm[0];
 }
 
-template <int PH>
-__global__ void __launch_bounds__(kBlock) k_multi_finish(MultiScal *S, const double *part, unsigned nwg)
+// the recurrence of dot group PH on one column's scalars, given the group's sums (one thread per column)
+template <int PH> static __device__ __forceinline__ void multi_recur(MultiScal *S, int col, double d0, double d1)
 {
-    __shared__ double sm[kBlock];
-    const int col = blockIdx.x;
-    if (PH != MP_INIT && !S->active[col]) return;
-    const double d0 = column_sum(part, 0, col, nwg, sm);
-    double d1 = 0.0;
-    if constexpr (PH == MP_OMEGA || PH == MP_END) d1 = column_sum(part, 1, col, nwg, sm);
-    if (threadIdx.x != 0) return;
     if constexpr (PH == MP_INIT) {             // (src/solver.c:78-83, 86)
         S->rTr[col] = d0; S->dot_r[col] = d0; S->dot_zero[col] = d0;
         S->rTr_old[col] = 0.0; S->alpha[col] = 0.0; S->omega[col] = 0.0; S->beta[col] = 0.0;
@@ -210,6 +204,62 @@ __global__ void __launch_bounds__(kBlock) k_multi_finish(MultiScal *S, const dou
         if (!(d0 > S->tol2 * S->dot_zero[col] && k < S->max_iter)) S->active[col] = 0;
         if (!(isfinite(alpha) && isfinite(beta) && isfinite(omega) && isfinite(d0)) && !S->breakdown[col]) S->breakdown[col] = k;
     }
+}
+
+template <int PH>
+__global__ void __launch_bounds__(kBlock) k_multi_finish(MultiScal *S, const double *part, unsigned nwg)
+{
+    __shared__ double sm[kBlock];
+    const int col = blockIdx.x;
+    if (PH != MP_INIT && !S->active[col]) return;
+    const double d0 = column_sum(part, 0, col, nwg, sm);
+    double d1 = 0.0;
+    if constexpr (PH == MP_OMEGA || PH == MP_END) d1 = column_sum(part, 1, col, nwg, sm);
+    if (threadIdx.x != 0) return;
+    multi_recur<PH>(S, col, d0, d1);
+}
+
+// Across ranks (bicg_solve_multi with nranks > 1) the finish is three steps: k_multi_sum, ONE all-reduce of red, k_multi_apply.
+// red[nranks][2][kSpmmCols]: k_multi_sum fills this rank's row with the local sums of all kSpmmCols columns (0.0 for a frozen or
+// unused column) and zeroes every other row, so the all-reduce adds each value to zeros only -- x + 0.0 is exact: it GATHERS every
+// rank's local sums, the same bytes on every rank whatever order the transport adds in.
+template <int PH>
+__global__ void __launch_bounds__(kBlock) k_multi_sum(const MultiScal *S, const double *part, unsigned nwg, int nv, double *red,
+                                                      int nranks, int rank)
+{
+    __shared__ double sm[kBlock];
+    const int col = blockIdx.x;                // grid: kSpmmCols workgroups, whatever nv is
+    const bool live = col < nv && (PH == MP_INIT || S->active[col]);      // workgroup-uniform
+    double d0 = 0.0, d1 = 0.0;
+    if (live) {
+        d0 = column_sum(part, 0, col, nwg, sm);
+        if constexpr (PH == MP_OMEGA || PH == MP_END) d1 = column_sum(part, 1, col, nwg, sm);
+    }
+    for (int t = threadIdx.x; t < 2 * nranks; t += kBlock) {
+        const int p = t >> 1, d = t & 1;
+        red[((size_t)p * 2 + d) * kSpmmCols + col] = p == rank ? (d ? d1 : d0) : 0.0;
+    }
+}
+
+// one thread per column: the ranks' local sums added in a fixed order, then the recurrence of k_multi_finish<PH>. The order is
+// rank_tree_sum's (bicg_devfn.h), the association of a recursive-doubling all-reduce ((s0 + s1) + (s2 + s3)) + ... -- ascending
+// rank order up to three ranks --: what the library's other sums over ranks use and what the reference's MPI_Iallreduce computes
+// under MPICH (oracle/bicg_oracle.c, orc_dist_dot), so that with one row per rank a column follows the reference bit for bit.
+// In place in red: k_multi_sum rewrites every entry before the next all-reduce.
+template <int PH>
+__global__ void __launch_bounds__(64) k_multi_apply(MultiScal *S, double *red, int nv, int nranks)
+{
+    const int col = threadIdx.x;
+    if (col >= nv) return;
+    if (PH != MP_INIT && !S->active[col]) return;
+    constexpr int row = 2 * kSpmmCols;
+    double *v0 = red + col, *v1 = red + kSpmmCols + col;
+    for (int stride = 1; stride < nranks; stride <<= 1)
+        for (int i = 0; i + stride < nranks; i += 2 * stride) {
+            v0[(size_t)i * row] += v0[(size_t)(i + stride) * row];
+            v1[(size_t)i * row] += v1[(size_t)(i + stride) * row];
+        }
+    multi_recur<PH>(S, col, v0[0], v1[0]);
 }
 
 template <int PH> static void run_multi(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st)
@@ -240,6 +290,28 @@ void launch_multi_finish(int phase, int nv, MultiScal *S, const double *part, un
     case MP_ALPHA: BICG_LAUNCH((k_multi_finish<MP_ALPHA>), g, b, 0, st, S, part, nwg); break;
     case MP_OMEGA: BICG_LAUNCH((k_multi_finish<MP_OMEGA>), g, b, 0, st, S, part, nwg); break;
     default:       BICG_LAUNCH((k_multi_finish<MP_END>), g, b, 0, st, S, part, nwg); break;
+    }
+}
+
+void launch_multi_sum(int phase, int nv, const MultiScal *S, const double *part, unsigned nwg, double *red, int nranks, int rank, hipStream_t st)
+{
+    const dim3 g((unsigned)kSpmmCols), b(kBlock);
+    switch (phase) {
+    case MP_INIT:  BICG_LAUNCH((k_multi_sum<MP_INIT>), g, b, 0, st, S, part, nwg, nv, red, nranks, rank); break;
+    case MP_ALPHA: BICG_LAUNCH((k_multi_sum<MP_ALPHA>), g, b, 0, st, S, part, nwg, nv, red, nranks, rank); break;
+    case MP_OMEGA: BICG_LAUNCH((k_multi_sum<MP_OMEGA>), g, b, 0, st, S, part, nwg, nv, red, nranks, rank); break;
+    default:       BICG_LAUNCH((k_multi_sum<MP_END>), g, b, 0, st, S, part, nwg, nv, red, nranks, rank); break;
+    }
+}
+
+void launch_multi_apply(int phase, int nv, MultiScal *S, double *red, int nranks, hipStream_t st)
+{
+    const dim3 g(1), b(64);
+    switch (phase) {
+    case MP_INIT:  BICG_LAUNCH((k_multi_apply<MP_INIT>), g, b, 0, st, S, red, nv, nranks); break;
+    case MP_ALPHA: BICG_LAUNCH((k_multi_apply<MP_ALPHA>), g, b, 0, st, S, red, nv, nranks); break;
+    case MP_OMEGA: BICG_LAUNCH((k_multi_apply<MP_OMEGA>), g, b, 0, st, S, red, nv, nranks); break;
+    default:       BICG_LAUNCH((k_multi_apply<MP_END>), g, b, 0, st, S, red, nv, nranks); break;
     }
 }
 

@@ -146,13 +146,13 @@ void group_enqueue(bicg_ctx *c, int n, int phase, hipEvent_t after)
 {
     if (c->comm->stream_ordered()) {
         BICG_HIP(hipStreamWaitEvent(c->sm, after, 0));
-        c->comm->allreduce_sum(c->S->red + c->pend_off, n, c->sm);
+        ctx_allreduce(c, c->S->red + c->pend_off, n, c->sm);
         launch_apply(c->S, phase, c->sm);
         hipEvent_t e = c->ev_red[c->i_red++ % kEvRing];
         BICG_HIP(hipEventRecord(e, c->sm));
         c->pend_ev = e;
     } else {
-        c->comm->allreduce_sum(c->S->red + c->pend_off, n, c->sc);   // synchronises sc
+        ctx_allreduce(c, c->S->red + c->pend_off, n, c->sc);   // synchronises sc
         launch_apply(c->S, phase, c->sc);
         c->pend_ev = nullptr;
     }
@@ -169,7 +169,7 @@ void group_now(bicg_ctx *c, int n, int phase)
         Section sec(c, SEC_REDUCE);
         const bicg_ctx::Group g = c->grp;
         grp_close(c, true);                                   // this rank's sums -> Scal::red
-        c->comm->allreduce_sum(c->S->red + g.off, g.n, c->sc);
+        ctx_allreduce(c, c->S->red + g.off, g.n, c->sc);
         launch_apply(c->S, g.phase, c->sc);
         return;
     }
@@ -186,7 +186,7 @@ void group_now(bicg_ctx *c, int n, int phase)
         return;
     }
     c->pend_off = 0;
-    c->comm->allreduce_sum(c->S->red, n, c->sc);
+    ctx_allreduce(c, c->S->red, n, c->sc);
     launch_apply(c->S, phase, c->sc);
 }
 
@@ -381,11 +381,11 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
             hipEvent_t ep = c->ev_pack[c->i_pack++ % kEvRing];
             BICG_HIP(hipEventRecord(ep, c->sc));
             BICG_HIP(hipStreamWaitEvent(c->sm, ep, 0));
-            c->comm->exchange(c->sendbuf, c->scnt.data(), c->sdsp.data(), xin + c->n_loc, c->rcnt.data(), c->rdsp.data(), c->sm);
+            ctx_exchange(c, c->sendbuf, c->scnt.data(), c->sdsp.data(), xin + c->n_loc, c->rcnt.data(), c->rdsp.data(), c->sm);
             eh = c->ev_halo[c->i_halo++ % kEvRing];
             BICG_HIP(hipEventRecord(eh, c->sm));
         } else {
-            c->comm->exchange(c->sendbuf, c->scnt.data(), c->sdsp.data(), xin + c->n_loc, c->rcnt.data(), c->rdsp.data(), c->sc);
+            ctx_exchange(c, c->sendbuf, c->scnt.data(), c->sdsp.data(), xin + c->n_loc, c->rcnt.data(), c->rdsp.data(), c->sc);
         }
         c->cur_sub = 0; sec_remark(c);
         bool joined_pending = false;
@@ -457,7 +457,29 @@ void halo_only(bicg_ctx *c, double *xin)
         return;
     }
     launch_halo_pack(xin, c->send_idx, c->nsend, c->sendbuf, c->S, c->sc);
-    c->comm->exchange(c->sendbuf, c->scnt.data(), c->sdsp.data(), xin + c->n_loc, c->rcnt.data(), c->rdsp.data(), c->sc);
+    ctx_exchange(c, c->sendbuf, c->scnt.data(), c->sdsp.data(), xin + c->n_loc, c->rcnt.data(), c->rdsp.data(), c->sc);
+}
+
+// The halo exchange of a set: nvec <= kSpmmCols vectors c->stride apart, ONE pack launch, ONE transport exchange, ONE unpack launch
+// instead of nvec of each (on the host transport every exchange ends in a stream synchronisation, on RCCL it is a grouped send /
+// recv). The buffers are peer-major (k_halo_pack_set), so the transport sees an ordinary exchange whose counts and displacements
+// are the context's times nvec. The halo tails receive exactly the values halo_only delivers: the products do not change by a bit.
+// Not for the peer-to-peer data path: its landing ring holds one vector per slot (spmm_pass keeps halo_only there).
+void halo_set(bicg_ctx *c, double *in, int nvec)
+{
+    if (c->single() || (c->halo == 0 && c->nsend == 0)) return;      // (halo_only's rule: such a rank has no part in the exchange)
+    if (!c->set_send) die("internal", "a set exchange without its buffers (spmm_buffers)");
+    const int P = c->nranks;
+    const std::vector<int> *src[4] = {&c->scnt, &c->sdsp, &c->rcnt, &c->rdsp};
+    for (int q = 0; q < 4; ++q) {
+        c->set_cnt[q].resize((size_t)P);
+        for (int p = 0; p < P; ++p) c->set_cnt[q][(size_t)p] = nvec * (*src[q])[(size_t)p];
+    }
+    launch_halo_pack_set(in, c->stride, nvec, c->send_idx, c->set_smap, c->nsend, c->set_send, c->S, c->sc);
+    ctx_exchange(c, c->set_send, c->set_cnt[0].data(), c->set_cnt[1].data(), c->set_recv, c->set_cnt[2].data(), c->set_cnt[3].data(), c->sc);
+    // (in + n_loc + j * stride + i, i < halo <= stride - n_loc: every write stays inside its own vector, the 64 doubles of slack
+    // behind the last vector of mm_in / mt_slab that k_spmm_pipe may read are never written)
+    launch_halo_unpack_set(c->set_recv, c->set_rmap, c->halo, nvec, in + c->n_loc, c->stride, c->S, c->sc);
 }
 
 // Y_j = (A + sigma_j I) X_j for nvec <= kSpmmCols vectors that sit shift-major in c->mm_in: one pass over A.
@@ -482,7 +504,9 @@ void spmm_pass(bicg_ctx *c, int nvec, const double *sigma_host, bool with_b, boo
     const size_t st = c->stride;
     if (!in) in = c->mm_in;
     if (!out) out = c->mm_yt;
-    for (int j = 0; j < nvec; ++j) halo_only(c, in + (size_t)j * st);
+    // the halos of the set in one exchange (BICG_PLAN="halo-set=0", read here: one exchange per vector, as on the peer-to-peer path)
+    if (!c->single() && !c->p2p && nvec > 1 && !plan_off("halo-set")) halo_set(c, in, nvec);
+    else for (int j = 0; j < nvec; ++j) halo_only(c, in + (size_t)j * st);
     // the windowed form (k_spmm_win) reads the shift-major vectors directly and writes Y shift-major into mm_yt
     const unsigned wslots = c->win_slots ? c->win_slots : (c->s_col16 && !c->sell_jag && c->fw.ncl > 0 ? c->fw.slots : 0u);
     c->mm_win = c->mm_win_env != 0 && spmm_win_vectors(wslots) > 0;
@@ -535,6 +559,18 @@ void spmm_buffers(bicg_ctx *c)
     c->mm_part = dev_alloc<double>((ngroups + 8) * kSpmmCols);
     c->mm_out = dev_alloc<double>(kSpmmCols);
     c->mm_sigma = dev_alloc<double>(kSpmmCols);
+    if (!c->single() && (c->halo || c->nsend)) {      // the set exchange (halo_set)
+        if ((uint64_t)kSpmmCols * std::max(c->halo, c->nsend) > 0x7fffffffull) die("bicg_spmm", "halo too long for a set exchange");
+        c->set_send = dev_alloc<double>((size_t)kSpmmCols * c->nsend);
+        c->set_recv = dev_alloc<double>((size_t)kSpmmCols * c->halo);
+        std::vector<uint2> sm(c->nsend), rm(c->halo);
+        for (int p = 0; p < c->nranks; ++p) {
+            for (int i = 0; i < c->scnt[(size_t)p]; ++i) sm[(size_t)(c->sdsp[(size_t)p] + i)] = make_uint2((unsigned)c->sdsp[(size_t)p], (unsigned)c->scnt[(size_t)p]);
+            for (int i = 0; i < c->rcnt[(size_t)p]; ++i) rm[(size_t)(c->rdsp[(size_t)p] + i)] = make_uint2((unsigned)c->rdsp[(size_t)p], (unsigned)c->rcnt[(size_t)p]);
+        }
+        c->set_smap = dev_upload(sm.data(), sm.size());
+        c->set_rmap = dev_upload(rm.data(), rm.size());
+    }
     BICG_HIP(hipMemset(c->mm_in, 0, sizeof(double) * kSpmmCols * st));
     BICG_HIP(hipDeviceSynchronize());      // the memset ran on the null stream: c->sc does not wait for it
     c->mm_xcd = !(knob_x("BICG_SPMM_XCD") && atoi(knob_x("BICG_SPMM_XCD")) == 0);

@@ -63,7 +63,7 @@ EXPORTS = [
     "bicg_run_begin", "bicg_run_iterate", "bicg_run_iterate_timed", "bicg_run_end", "bicg_sync", "bicg_trace", "bicg_spmv", "bicg_dot", "bicg_spmv_bench", "bicg_plan_info", "bicg_ctx_flags", "bicg_spmm", "bicg_device_matrix_bytes", "bicg_uniform_entries", "bicg_constant_entries", "bicg_masked_rows", "bicg_stencil_info", "bicg_stencil_rows_per_lane", "bicg_comm_wait_stats", "bicg_plan_collisions", "bicg_product_kernels", "bicg_spmv_matrix_bytes", "bicg_last_shifted_persistent", "bicg_last_spmm_windowed", "bicg_dropin_context", "bicg_dropin_release", "bicg_dropin_stats",
     "bicg_mtx_load_block", "bicg_mtx_free", "bicg_partition", "bicg_halo_plan", "bicg_halo_send_counts", "bicg_halo_send_lists", "bicg_row_blocks", "bicg_window_plan", "bicg_window_slot", "bicg_version", "bicg_has_experiments", "bicg_switch_value", "bicg_switch_unknown", "bicg_stream_bench", "bicg_create_device_csr", "bicg_stencil7_device", "bicg_device_free", "bicg_persist_plan", "bicg_set_plan_threads", "bicg_sell_plan_digest",
     "bicg_reorder_plan", "bicg_permute_block", "bicg_reorder_info",
-    "bicg_solve_multi", "bicg_multi_trace",
+    "bicg_solve_multi", "bicg_multi_trace", "bicg_comm_counts",
 ]
 
 _lib = None
@@ -97,6 +97,8 @@ def lib():
         L.bicg_solve_multi.restype = C.c_int
         L.bicg_multi_trace.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
         L.bicg_multi_trace.restype = C.c_int
+        L.bicg_comm_counts.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+        L.bicg_comm_counts.restype = C.c_int
         L.bicg_spmv.argtypes = [C.c_void_p, _dp, _dp]
         L.bicg_dot.argtypes = [C.c_void_p, _dp, _dp]
         L.bicg_dot.restype = C.c_double
@@ -160,7 +162,7 @@ def lib():
 # The library's token-list variables (csrc/bicg_knobs.h): keyword -> (variable, token). INTEGRATION.md section 6 says what each does.
 SWITCHES = {k: ("BICG_PLAN", k.replace("_", "-")) for k in (
     "stencil", "lines", "planes", "ca_fuse", "layout", "window", "col16", "uniform", "constant", "masked", "desc", "lists", "jagw",
-    "spmm", "spmm_window", "fuse_pipe", "pipe_probe", "halo_fused", "window_list", "wide", "reorder", "handover")}
+    "spmm", "spmm_window", "fuse_pipe", "pipe_probe", "halo_fused", "window_list", "wide", "reorder", "handover", "halo_set")}
 SWITCHES.update(persist=("BICG_PERSIST", "0"), persist_chunk=("BICG_PERSIST", "chunk"), persist_shifted=("BICG_PERSIST", "shifted"),
                 force_comm=("BICG_TEST", "force-comm"), spin_ticks=("BICG_TEST", "spin-ticks"),
                 p2p_fault_after=("BICG_TEST", "p2p-fault-after"), plan_collide=("BICG_TEST", "plan-collide"))
@@ -333,12 +335,17 @@ class Context:
         k = lib().bicg_solve(self.h, METHODS[method], _d(x), _d(r), C.byref(o), C.byref(res))
         return dict(k=k, x=x, r=r, dot_r=res.dot_r, dot_zero=res.dot_zero, result=res)
 
-    def solve_multi(self, B, X0=None, method: str = "bicgstab", **kw):
+    def solve_multi(self, B, X0=None, method: str = "bicgstab", nrhs=None, **kw):
         """Plain BiCGStab on the rows of B [nrhs][n] as independent right-hand sides of the resident matrix, 16 columns per pass
         over the matrix (bicg_solve_multi): dict(k [nrhs] int array, x [nrhs][n], r [nrhs][n], results [nrhs] of Result, rc = the
-        call's return value: the largest k, or the negative code of a refused call -- x and r are then X0 and B)."""
-        r = np.array(B, dtype=np.float64).reshape(-1, self.n)
-        nrhs = r.shape[0]
+        call's return value: the largest k, or the negative code of a refused call -- x and r are then X0 and B). Collective
+        across ranks (rc = -1: the ranks passed different arguments); nrhs: the number of columns where B cannot tell -- a rank
+        without rows (n = 0) passes it with empty arrays."""
+        if nrhs is None:
+            r = np.array(B, dtype=np.float64).reshape(-1, self.n)
+            nrhs = r.shape[0]
+        else:
+            r = np.array(B, dtype=np.float64).reshape(nrhs, self.n)
         x = np.zeros((nrhs, self.n)) if X0 is None else np.array(X0, dtype=np.float64).reshape(nrhs, self.n)
         kw.setdefault("quiet", 1)
         o = self.options(**kw)
@@ -463,6 +470,12 @@ class Context:
         ms = C.c_double(0.0)
         lib().bicg_spmv_bench(self.h, reps, C.byref(ms))
         return ms.value
+
+    def comm_counts(self):
+        """transport collectives issued for this context since it was created (bicg_comm_counts): dict(exchanges, allreduces)"""
+        out = (C.c_ulonglong * 2)()
+        lib().bicg_comm_counts(self.h, out)
+        return dict(exchanges=int(out[0]), allreduces=int(out[1]))
 
     def comm_failed(self) -> bool:
         return bool(lib().bicg_comm_failed(self.h))

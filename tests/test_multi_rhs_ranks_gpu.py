@@ -1,0 +1,128 @@
+"""`-m gpu`: bicg_solve_multi across ranks (csrc/bicg_multi.cpp): 2, 3 and 8 spawned ranks share the one
+GPU through the host-staged transport and solve sets of right-hand sides collectively -- one halo exchange per set and product
+(k_halo_pack_set / k_halo_unpack_set), one all-reduce per dot group that gathers every rank's local sums (k_multi_sum /
+k_multi_apply). The workers: tests/mp_multi_workers.py.
+
+Inputs: the matrices of mp_workers.test_matrix over synth.split_blocks; b_j = A x*_j with the solutions() family of
+tests/test_multi_rhs_gpu.py (ones, zero, a unit vector, a step, then 0.5 + rng(7)); tol = 1e-12.
+
+Bars, from tests/test_multi_rhs_gpu.py, against the oracle's solve of every column AT THE SAME RANK COUNT: |k - k_oracle| <= 2, the
+first min(6, k) trace entries at rtol 1e-8, |x - x*|_inf <= 1e-9. The oracle alone, 1 rank against P = 2, 3, 4, 8 on these inputs,
+moves its first six trace entries by <= 1.3e-12 relative and its k by at most 1 ("ragged"). "ragged" is singular (5 % empty rows;
+the oracle's own |x - x*| is 128): there x is compared with the oracle's x at the same P, |x - x_o|_inf <= 1e-8 max(1, |x_o|_inf),
+a measure on which the oracle itself moves by 2e-11. Everything else is compared as bytes.
+
+Not exercised here: RCCL with more than one rank (it refuses two ranks on one device) and any real link between GPUs."""
+import functools
+import glob
+import os
+import socket
+import tempfile
+import time
+
+import numpy as np
+import pytest
+import torch.multiprocessing as mp
+
+import mp_multi_workers as W
+import oracle_lib as O
+from test_multi_rhs_gpu import solutions
+
+pytestmark = pytest.mark.gpu
+WALL_LIMIT = 240.0      # seconds per case
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    return port
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, world, nrhs):
+    """x*, B and the oracle's solve of every column over `world` virtual ranks -- computed once, never written to"""
+    A = W.matrix(name)
+    row, col, val = A.to_coo()
+    xs = solutions(A.rows, nrhs)
+    B = np.array([O.spmv(A.rows, row, col, val, x) for x in xs])
+    orc = [O.solve("bicgstab", A.rows, row, col, val, b, nranks=world, tol=W.TOL) for b in B]
+    kmax = max(max(o["k"] for o in orc), 1)
+    out = dict(xs=xs, B=B, k=np.array([o["k"] for o in orc]), x=np.array([o["x"] for o in orc]))
+    for key in ("alpha", "omega", "beta", "dotr"):
+        out[key] = np.array([np.pad(o[key], (0, kmax - o["k"])) for o in orc])
+    for a in out.values():
+        a.setflags(write=False)
+    return out
+
+
+def _run(case, name, world, nrhs):
+    with tempfile.TemporaryDirectory() as td:
+        np.savez(os.path.join(td, "oracle.npz"), **reference(name, world, nrhs))
+        procs = mp.start_processes(W.multi_worker, args=(world, _free_port(), f"{case}:{name}", td), nprocs=world, join=False,
+                                   start_method="spawn")
+        t0, error = time.monotonic(), None
+        try:
+            while not procs.join(timeout=2.0):
+                if time.monotonic() - t0 > WALL_LIMIT:
+                    error = f"the ranks were still running after {WALL_LIMIT:.0f} s"
+                    break
+        except Exception as e:      # a rank raised: join() has ended the others
+            error = str(e)
+        for p in procs.processes:
+            if p.is_alive():
+                p.terminate()
+        for p in procs.processes:
+            p.join(10)
+            if p.is_alive():
+                p.kill()
+        fails = sorted(glob.glob(os.path.join(td, "fail*")))
+        assert not fails, open(fails[0]).read()
+        assert error is None, error
+        skips = sorted(glob.glob(os.path.join(td, "skip*")))
+        if skips:
+            pytest.skip(open(skips[0]).read())
+        assert len(glob.glob(os.path.join(td, "ok*"))) == world
+
+
+@pytest.mark.parametrize("name,world,nrhs", [("offsets", 2, 21), ("offsets", 3, 21), ("stencil", 2, 16), ("stencil", 3, 16), ("ragged", 2, 5)])
+def test_oracle_bars_and_the_same_bytes_on_every_rank(name, world, nrhs):
+    """cases 1 and 2: the oracle's bars on every rank's rows (column 1, b = 0: k = 0, x = 0; the stencil's columns stop at three or more
+    different iterations; rc = max k; "ragged" without the SpMM); k, dot_r, dot_zero, breakdown_iteration and the four traces of
+    every column are the same bytes on every rank, and a second run gives the bytes of the first"""
+    _run("oracle", name, world, nrhs)
+
+
+def test_a_column_does_not_know_its_neighbours_at_three_ranks():
+    """case 3: the fastest and the slowest column, column 1 and column 18 (second set), each alone as a one-column collective call,
+    equal their state in the 21-column call bit for bit; check_every 1 and 7 give the same bytes"""
+    _run("neighbours", "offsets", 3, 21)
+
+
+def test_one_exchange_per_set_and_one_allreduce_per_dot_group():
+    """cases 4 and 5: tol = 0, max_iter = 3, check_every = 1 on 16 columns: 1 + 2 x 3 transport exchanges per rank, 7 x 16 under
+    halo-set=0, the same bytes either way and under spmm=0; bicg_spmm of 16 vectors: 1 exchange against 16, same bytes; the
+    all-reduces of the call are as many on every rank and no more for 16 columns than for 1"""
+    _run("counts", "offsets", 2, 16)
+
+
+def test_ranks_without_rows_take_part():
+    """case 6: 6 rows over 8 ranks, 3 columns; ranks 6 and 7 call with nrhs = 3 and empty arrays; every rank gets the same k.
+    A 6 x 6 system ends at k = 6 with a sixth iteration made of rounding noise ((r,r) = 4e-45): the oracle's own sixth omega moves by
+    3e-3 relative between 1 and 8 virtual ranks, and sums over ranks in ascending order gave 0.18694644 against its 0.19148523. The
+    trace bar holds at that entry because k_multi_apply adds the ranks' sums in the oracle's order (recursive doubling) and a rank
+    holds one row here, so the whole recurrence is the oracle's bit for bit."""
+    _run("empty", "six", 8, 3)
+
+
+def test_disagreeing_ranks_get_minus_one_and_stay_in_step():
+    """case 7: 5 columns on rank 0, 3 on rank 1 -> -1 on both, x and r untouched; another method on both -> -2; a correct call
+    right afterwards still meets the oracle's bars"""
+    _run("disagree", "offsets", 2, 21)
+
+
+def test_peer_to_peer_context():
+    """case 8: after bicg_comm_enable_p2p() 16 columns meet the oracle's bars and one column alone equals its state in the set
+    (skipped with the library's code when the peer-to-peer path does not come up)"""
+    _run("p2p", "offsets", 2, 16)
