@@ -419,6 +419,11 @@ unsigned int bicg_stencil_rows_per_lane(bicg_ctx *ctx);
  * list it was given: the number of slices that did NOT match (hash collisions) and were put back on their stored columns and
  * values. 0 for contexts built by bicg_create (the host plan keys on the full lists). */
 unsigned int bicg_plan_collisions(bicg_ctx *ctx);
+/* Device allocations this process has made through the library's host code and not yet freed: the contexts' matrix, plan,
+ * vectors and lazily grown buffers (traces, shift sets, SpMM / multi-RHS sets, staging) and the temporaries of a call in progress.
+ * Not counted: the transports' own memory (the landing ring among it) and what bicg_stencil7_device hands to the caller. The
+ * count after bicg_destroy equals the count before the matching bicg_create, whatever was called in between. */
+long long bicg_device_allocations(void);
 /* Which product kernels this process has launched since the last call with reset != 0 (bit mask): 1 k_spmv_sell on padded slices,
  * 2 k_spmv_sell on jagged slices (columns gathered through the caches), 4 k_spmv_sell's loop over jagged slices with the x window
  * in LDS, 8 k_spmv_jagw (the three-trip form of that product, csrc/bicg_jagw.hip), 16 k_spmv_stencil, 32 k_spmv (CSR row blocks),

@@ -8,8 +8,8 @@ static void reorder_stage(bicg_ctx *c, int nvec)
 {
     const int want = std::min(nvec, kSpmmCols);
     if (c->ro_stage_vecs >= want) return;
-    if (c->ro_stage) { BICG_HIP(hipStreamSynchronize(c->sc)); BICG_HIP(hipFree(c->ro_stage)); }
-    c->ro_stage = dev_alloc<double>((size_t)want * c->stride);
+    if (c->ro_stage) BICG_HIP(hipStreamSynchronize(c->sc));
+    c->ro_stage = c->own.regrow(c->ro_stage, (size_t)want * c->stride);
     c->ro_stage_vecs = want;
 }
 void reorder_upload(bicg_ctx *c, double *dev, size_t dev_stride, const double *host, int nvec, bool async)
@@ -308,13 +308,14 @@ int bicg_comm_wait_stats(bicg_ctx *c, double out[6])
 int bicg_stencil_info(bicg_ctx *c, unsigned int out[8])
 {
     const bool on = stencil_product(c);
-    const StencilDev &t = c->st;
+    const StencilDev &t = c->sell.st;
     const unsigned int v[8] = {on ? 1u : 0u, t.sy, t.ny, t.nz, t.lines, t.zl, on ? stencil_grid(t) : 0u, t.nmc};
     for (int i = 0; i < 8; ++i) out[i] = v[i];
     return on ? 1 : 0;
 }
-unsigned int bicg_stencil_rows_per_lane(bicg_ctx *c) { return stencil_product(c) ? (c->st.wide ? c->st.wide : 1u) : 0u; }
+unsigned int bicg_stencil_rows_per_lane(bicg_ctx *c) { return stencil_product(c) ? (c->sell.st.wide ? c->sell.st.wide : 1u) : 0u; }
 unsigned int bicg_plan_collisions(bicg_ctx *c) { return c->plan_collisions; }
+long long bicg_device_allocations(void) { return dev_live(); }
 int bicg_reorder_info(bicg_ctx *c, unsigned long long out[8])
 {
     for (int i = 0; i < 8; ++i) out[i] = c->reordered ? c->ro_stats[i] : 0ull;
@@ -336,9 +337,9 @@ unsigned int bicg_ctx_flags(bicg_ctx *c)
     if (c->p2p) f |= BICG_FLAG_P2P;
     if (c->ll_fused) f |= BICG_FLAG_LL_FUSED;
     if (c->overlap) f |= BICG_FLAG_OVERLAP;
-    if (c->s_col16) f |= BICG_FLAG_COL16;
-    if (c->sell_jag) f |= BICG_FLAG_JAGGED;
-    if (c->win_slots) f |= BICG_FLAG_WINDOW;
+    if (c->sell.col16) f |= BICG_FLAG_COL16;
+    if (c->sell.jag) f |= BICG_FLAG_JAGGED;
+    if (c->sell.win_slots) f |= BICG_FLAG_WINDOW;
     if (c->spmm_ok) f |= BICG_FLAG_SPMM;
     if (c->glist_all) f |= BICG_FLAG_ALL_SELL;
     if (c->rowsplit) f |= BICG_FLAG_ROWSPLIT;

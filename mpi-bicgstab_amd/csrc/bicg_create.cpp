@@ -49,8 +49,8 @@ static void build_slice_desc(bicg_ctx *c, uint32_t nslices, uint32_t nrows, cons
     if (all_lists) {                              // (SellDev::all_lists: the distances once more, as byte offsets)
         std::vector<int> u8(uoff.size());
         for (size_t i = 0; i < uoff.size(); ++i) u8[i] = (int)((uint32_t)uoff[i] * 8u);      // (modulo 2^32: the product adds it to the row's byte offset modulo 2^32)
-        c->s_uoff8 = dev_upload(u8.data(), u8.size());
-        c->sell_all_lists = true;
+        c->sell.uoff8 = c->own.upload(u8.data(), u8.size());
+        c->sell.all_lists = 1;
         // SellDev::ystride from the longest list (the interior's): its second-largest distance is a grid line when it is a multiple
         // of 64 rows. (Only the speed depends on the guess: any value gives every slice to exactly one wavefront.)
         uint32_t best_len = 0, best_at = 0;
@@ -61,10 +61,10 @@ static void build_slice_desc(bicg_ctx *c, uint32_t nslices, uint32_t nrows, cons
             std::sort(dist.begin(), dist.end());
             const int line = dist[best_len - 2];
             const uint32_t S = line > 0 ? (uint32_t)line / kSliceRows : 0u;
-            if (S >= 1 && (uint32_t)line % kSliceRows == 0 && (S & (S - 1u)) == 0 && nslices % (4u * S) == 0) c->sell_ystride = (int)S;   // (a power of two: shifts in the kernel)
+            if (S >= 1 && (uint32_t)line % kSliceRows == 0 && (S & (S - 1u)) == 0 && nslices % (4u * S) == 0) c->sell.ystride = (int)S;   // (a power of two: shifts in the kernel)
         }
     }
-    c->s_desc = dev_upload(d.data(), d.size());
+    c->sell.sdesc = c->own.upload(d.data(), d.size());
     if (all_lists) build_stencil_plan(c, nslices, nrows, d, uoff, uval, rmask_host);
 }
 
@@ -126,7 +126,7 @@ static void build_stencil_plan(bicg_ctx *c, uint32_t nslices, uint32_t nrows, co
             uint32_t top = 0;
             for (uint32_t sl = 0; sl < nslices; ++sl) if ((d[sl].x >> 16) == kSliceMasked) top = std::max(top, d[sl].w + 1u);
             rm_dl.resize((size_t)top * kSliceRows);
-            BICG_HIP(hipMemcpy(rm_dl.data(), c->s_rmask, sizeof(unsigned short) * rm_dl.size(), hipMemcpyDeviceToHost));
+            BICG_HIP(hipMemcpy(rm_dl.data(), c->sell.rmask, sizeof(unsigned short) * rm_dl.size(), hipMemcpyDeviceToHost));
             rmask_host = rm_dl.data();
         }
         cmask.assign((size_t)(nslices / nxs) * nmc * kSliceRows, 0);
@@ -194,6 +194,7 @@ static void build_stencil_plan(bicg_ctx *c, uint32_t nslices, uint32_t nrows, co
             else if (c->rank == 0) fprintf(stderr, "bicgstab_hip: BICG_PLAN planes=%s ignored (%llu workgroups, room for %llu partial-sum rows)\n", v, (unsigned long long)wgs, (unsigned long long)room);
         }
     }
+    const uint32_t *wbits_d = nullptr;
     if (wide) {
         std::vector<uint32_t> wb((size_t)nz * nxt * ny);
         parallel_ranges(wb.size(), 65536, [&](size_t i0, size_t i1, int) {
@@ -204,11 +205,11 @@ static void build_stencil_plan(bicg_ctx *c, uint32_t nslices, uint32_t nrows, co
                 wb[i] = word;
             }
         });
-        c->st_wbits = dev_upload(wb.data(), wb.size());
+        wbits_d = c->own.upload(wb.data(), wb.size());
     }
-    c->st_code = dev_upload(code.data(), code.size());
-    c->st_tab = dev_upload(tab.data(), tab.size());
-    if (nmc) c->st_cmask = dev_upload(cmask.data(), cmask.size());
+    const uint32_t *code_d = c->own.upload(code.data(), code.size());
+    const StencilTab *tab_d = c->own.upload(tab.data(), tab.size());
+    const unsigned char *cmask_d = nmc ? c->own.upload(cmask.data(), cmask.size()) : nullptr;
     // Input + output vector far beyond the 256 MiB Infinity Cache (512^3: 2 x 1 GiB): y is stored non-temporally and the tiles go to
     // the XCDs round-robin (product 0.480 -> 0.460 ms, CA-BiCGStab 5.40 -> 5.31 ms per iteration); a grid whose vectors the cache
     // holds (256^3) keeps ordinary stores and the XCD-contiguous order (0.053 against 0.061 ms): profiles/r05/stencil_sweep_xcd_nt.txt
@@ -218,14 +219,14 @@ static void build_stencil_plan(bicg_ctx *c, uint32_t nslices, uint32_t nrows, co
     int st_xcd = knob_x("BICG_STENCIL_XCD") ? atoi(knob_x("BICG_STENCIL_XCD")) : (st_big ? (wide ? 2 : 0) : 1);
     if (st_xcd == 2 && ((ny + 4 * lines - 1) / (4 * lines)) % 8u) st_xcd = st_big ? 0 : 1;       // (the sweep order deals whole line blocks to the XCDs)
     const int st_nt = knob_x("BICG_STENCIL_NT") ? atoi(knob_x("BICG_STENCIL_NT")) : (st_big ? 1 : 0);
-    c->st = StencilDev{1, sy, sz, nxs, ny, nz, 0u, nz, zl, lines, nmc, st_xcd, st_nt, mcols, c->st_code, c->st_tab, c->st_cmask, wide, ref, c->st_wbits};
+    c->sell.st = StencilDev{1, sy, sz, nxs, ny, nz, 0u, nz, zl, lines, nmc, st_xcd, st_nt, mcols, code_d, tab_d, cmask_d, wide, ref, wbits_d};
     if (const char *v = plan_tok("ca-fuse")) c->ca_fuse = atoi(v) != 0;
     // what this product streams from the matrix side: 4 bytes per slice, one byte per row of the masked x segments
     // (the wide form: 4 bytes per `wide` slices)
     c->stencil_matrix_bytes = 4ull * nslices / (wide ? wide : 1u) + (uint64_t)cmask.size();
     if (plan_trace_env())
         fprintf(stderr, "bicgstab_hip: plane-marching product: %u x %u x %u grid (x segments of 64 rows: %u), %zu list pairs, %u masked x segments, %u lines x %u planes per wavefront, %u rows per lane, %u workgroups\n",
-                sy, ny, nz, nxs, tab.size(), nmc, lines, zl, wide ? wide : 1u, stencil_grid(c->st));
+                sy, ny, nz, nxs, tab.size(), nmc, lines, zl, wide ? wide : 1u, stencil_grid(c->sell.st));
 }
 
 
@@ -260,8 +261,8 @@ void sell_order_for_big_grids(bicg_ctx *c, uint32_t ngroups)
             for (uint64_t z0 = s0; z0 < s1; z0 += P)
                 for (uint64_t g = z0 + y0; g < std::min<uint64_t>({(uint64_t)s1, z0 + y0 + B, z0 + P}); ++g) list[o++] = (uint32_t)g;
     }
-    if (c->glist_int) BICG_HIP(hipFree(c->glist_int));
-    c->glist_int = dev_upload(list.data(), list.size());
+    c->own.free(c->glist_int);
+    c->glist_int = c->own.upload(list.data(), list.size());
     c->glist_int_identity = false;
     c->sell_blocked = B;
 }
@@ -306,24 +307,24 @@ bool persist_build(bicg_ctx *c, const CSR_Matrix *diag, const std::vector<uint32
     const unsigned lds_max = std::min<unsigned>(kPersistMaxLds, prop.sharedMemPerBlock > 8192 ? (unsigned)prop.sharedMemPerBlock - 6144u : 0u);
     if (persist_lds_bytes(a) > lds_max) a.mat_entries = 0;
     if (persist_lds_bytes(a) > lds_max) { a = PersistArgs{}; return false; }
-    auto keep = [&](void *p) { c->persist_mem.push_back(p); return p; };
-    a.pval = (const double *)keep(dev_upload(pval.data(), pval.size()));
-    a.pslot = (const unsigned short *)keep(dev_upload(pslot.data(), pslot.size()));
-    a.pbase = (const uint32_t *)keep(dev_upload(pbase.data(), pbase.size()));
-    a.rlen = (const unsigned short *)keep(dev_upload(rlen.data(), rlen.size()));
-    a.rdiag = (const unsigned short *)keep(dev_upload(rdiag.data(), rdiag.size()));
-    a.win_ptr = (const uint32_t *)keep(dev_upload(wptr.data(), wptr.size()));
-    a.win_runs = (const uint2 *)keep(dev_upload(runs.data(), runs.size()));
+    DevOwner &own = c->persist_own;
+    a.pval = own.upload(pval.data(), pval.size());
+    a.pslot = own.upload(pslot.data(), pslot.size());
+    a.pbase = own.upload(pbase.data(), pbase.size());
+    a.rlen = own.upload(rlen.data(), rlen.size());
+    a.rdiag = own.upload(rdiag.data(), rdiag.size());
+    a.win_ptr = own.upload(wptr.data(), wptr.size());
+    a.win_runs = own.upload(runs.data(), runs.size());
     for (int i = 0; i < 4; ++i) {
-        a.llv[i] = (llword *)keep(dev_alloc<llword>(2 * (size_t)nrows));
+        a.llv[i] = own.alloc<llword>(2 * (size_t)nrows);
         BICG_HIP(hipMemset(a.llv[i], 0, sizeof(llword) * 2 * (size_t)nrows));
     }
     for (int i = 0; i < 2; ++i) {
-        a.dtab[i] = (llword *)keep(dev_alloc<llword>((size_t)nwg * kRedSlots * 2));
+        a.dtab[i] = own.alloc<llword>((size_t)nwg * kRedSlots * 2);
         BICG_HIP(hipMemset(a.dtab[i], 0, sizeof(llword) * (size_t)nwg * kRedSlots * 2));
-        a.arow[i] = (llword *)keep(dev_alloc<llword>(8));
+        a.arow[i] = own.alloc<llword>(8);
         BICG_HIP(hipMemset(a.arow[i], 0, sizeof(llword) * 8));
-        a.crow[i] = (llword *)keep(dev_alloc<llword>(6 * kPersistMaxShifts * 2));      // shifted kernel: per-shift coefficients
+        a.crow[i] = own.alloc<llword>(6 * kPersistMaxShifts * 2);      // shifted kernel: per-shift coefficients
         BICG_HIP(hipMemset(a.crow[i], 0, sizeof(llword) * 6 * kPersistMaxShifts * 2));
     }
     a.multi = multi ? 1 : 0;
@@ -339,10 +340,10 @@ bool persist_build(bicg_ctx *c, const CSR_Matrix *diag, const std::vector<uint32
             const uint32_t g = send_idx[i] / grows, at = fill[g]++;
             srow[at] = (unsigned short)(send_idx[i] - g * grows); sd0[at] = dst0[i]; sst[at] = dstride[i];
         }
-        a.snd_ptr = (const uint32_t *)keep(dev_upload(sptr.data(), sptr.size()));
-        a.snd_row = (const unsigned short *)keep(dev_upload(srow.data(), srow.size()));
-        a.snd_dst0 = (const unsigned long long *)keep(dev_upload(sd0.data(), sd0.size()));
-        a.snd_stride = (const unsigned long long *)keep(dev_upload(sst.data(), sst.size()));
+        a.snd_ptr = own.upload(sptr.data(), sptr.size());
+        a.snd_row = own.upload(srow.data(), srow.size());
+        a.snd_dst0 = own.upload(sd0.data(), sd0.size());
+        a.snd_stride = own.upload(sst.data(), sst.size());
         a.ring = c->halo_ring; a.halo = c->halo;
     }
     a.v = c->v;
@@ -363,7 +364,7 @@ static void ctx_state(bicg_ctx *c, Comm *comm, uint32_t ngroups)
     // (BICG_STRIDE_PAD = doubles added to the distance between two vectors, a multiple of 32: measurement knob for grids whose
     // vectors would otherwise lie a power of two bytes apart -- 512^3: exactly 1 GiB)
     if (const char *sv = knob_x("BICG_STRIDE_PAD")) c->stride += ((uint32_t)std::max(0, atoi(sv)) / 32u) * 32u;
-    c->slab = dev_alloc<double>(12 * (size_t)c->stride);
+    c->slab = c->own.alloc<double>(12 * (size_t)c->stride);
     BICG_HIP(hipMemset(c->slab, 0, sizeof(double) * 12 * (size_t)c->stride));
     double *base = c->slab;
     double **slots[12] = {&c->v.x, &c->v.r, &c->v.rh, &c->v.p, &c->v.s, &c->v.y, &c->v.z, &c->v.w, &c->v.v, &c->v.t, &c->v.ax, &c->v.b};
@@ -371,27 +372,27 @@ static void ctx_state(bicg_ctx *c, Comm *comm, uint32_t ngroups)
     c->v.n = c->n_loc;
 
     c->nslots = std::max<unsigned>(ngroups + c->nblk, kMaxGrid) + 64;
-    c->partial = dev_alloc<double>((size_t)c->nslots * kPartialStride);
-    c->shard_tot = dev_alloc<double>((size_t)kShards * kPartialStride);
-    c->counter = dev_alloc<unsigned>((kShards + 1) * kCounterStride);
+    c->partial = c->own.alloc<double>((size_t)c->nslots * kPartialStride);
+    c->shard_tot = c->own.alloc<double>((size_t)kShards * kPartialStride);
+    c->counter = c->own.alloc<unsigned>((kShards + 1) * kCounterStride);
     BICG_HIP(hipMemset(c->counter, 0, sizeof(unsigned) * (kShards + 1) * kCounterStride));
-    c->tail_tab = dev_alloc<llword>((size_t)c->nslots * kTailStride);
+    c->tail_tab = c->own.alloc<llword>((size_t)c->nslots * kTailStride);
     BICG_HIP(hipMemset(c->tail_tab, 0, sizeof(llword) * (size_t)c->nslots * kTailStride));
-    c->tail_shard = dev_alloc<llword>((size_t)kShards * kRedSlots * 2);
+    c->tail_shard = c->own.alloc<llword>((size_t)kShards * kRedSlots * 2);
     BICG_HIP(hipMemset(c->tail_shard, 0, sizeof(llword) * kShards * kRedSlots * 2));
     if (const char *sv = knob_x("BICG_TAIL_FINISH")) c->tail_finish = atoi(sv) != 0;
-    c->hand_shard = dev_alloc<llword>((size_t)2 * kRedSlots * kShards * 2);
+    c->hand_shard = c->own.alloc<llword>((size_t)2 * kRedSlots * kShards * 2);
     BICG_HIP(hipMemset(c->hand_shard, 0, sizeof(llword) * 2 * kRedSlots * kShards * 2));
-    c->Sbuf = dev_alloc<Scal>(2);
+    c->Sbuf = c->own.alloc<Scal>(2);
     BICG_HIP(hipMemset(c->Sbuf, 0, 2 * sizeof(Scal)));
     c->S = c->Sbuf;
     for (int i = 0; i < 2; ++i) {
-        c->wpart[i] = dev_alloc<double>((size_t)c->nslots * (kBlock / 64) * kPartialStride);
+        c->wpart[i] = c->own.alloc<double>((size_t)c->nslots * (kBlock / 64) * kPartialStride);
         BICG_HIP(hipMemset(c->wpart[i], 0, sizeof(double) * (size_t)c->nslots * (kBlock / 64) * kPartialStride));
     }
-    c->shard_ll = dev_alloc<llword>((size_t)2 * kShardLL * kRedSlots * 2);
+    c->shard_ll = c->own.alloc<llword>((size_t)2 * kShardLL * kRedSlots * 2);
     BICG_HIP(hipMemset(c->shard_ll, 0, sizeof(llword) * 2 * kShardLL * kRedSlots * 2));
-    c->alarm = dev_alloc<int>(1);
+    c->alarm = c->own.alloc<int>(1);
     BICG_HIP(hipMemset(c->alarm, 0, sizeof(int)));
     BICG_HIP(hipHostMalloc((void **)&c->h_alarm, sizeof(int), hipHostMallocDefault));
     *c->h_alarm = 0;
@@ -454,12 +455,10 @@ void bicg_default_options(bicg_options *o)
 static void preload_for(bicg_ctx *c)
 {
     if (knob_x("BICG_PRELOAD") && atoi(knob_x("BICG_PRELOAD")) == 0) return;
-    SellDev d = {c->s_val, c->s_col, c->s_base, c->s_len, c->s_col16, c->s_base16, c->sell_jag ? 1 : 0, c->win_ptr, c->win_runs, c->win_slots, c->sell_perm};
-    d.vbase = c->s_vbase;
-    preload_kernels(d, c->sell_entries > 0);
+    preload_kernels(c->sell, c->sell_entries > 0);
     if (c->persist_on) preload_persist_kernels();
-    if (c->st.on) preload_stencil_kernels();
-    if (c->lane_info && c->jagw_fast) preload_jagw_kernels();
+    if (c->sell.st.on) preload_stencil_kernels();
+    if (c->sell.lane_info && c->jagw_fast) preload_jagw_kernels();
 }
 
 // switches both constructors read into the context
@@ -503,7 +502,7 @@ static void ctx_finish(bicg_ctx *c, Comm *comm, uint32_t ngroups, const CSR_Matr
         bool mine = !off && persist_build(c, diag, host->optr, host->ocol, host->oval, host->send_idx, host->dst0, host->dstride);
         c->persist_on = all_ranks(comm, mine);
         if (const char *pp = knob_x("BICG_PERSIST_PLAIN")) c->persist_plain = atoi(pp) != 0;
-        if (!c->persist_on && mine) { for (void *p : c->persist_mem) (void)hipFree(p); c->persist_mem.clear(); c->persist = PersistArgs{}; }
+        if (!c->persist_on && mine) { c->persist_own.clear(); c->persist = PersistArgs{}; }
     }
     trace.mark("transport, persistent plan");
     ctx_streams(c, c->nranks);
@@ -617,8 +616,8 @@ static const CSR_Matrix *reorder_block(bicg_ctx *c, const CSR_Matrix *diag, cons
     }
     c->reordered = true;
     memcpy(c->ro_stats, stats, sizeof stats);
-    c->ro_perm = dev_upload(perm.data(), perm.size());
-    c->ro_inv = dev_upload(inv.data(), inv.size());
+    c->ro_perm = c->own.upload(perm.data(), perm.size());
+    c->ro_inv = c->own.upload(inv.data(), inv.size());
     return &ro;
 }
 
@@ -634,9 +633,11 @@ static void sell_plan_upload(bicg_ctx *c, const CSR_Matrix *diag, const SellPlan
     const uint32_t nrows = p.nrows, nslices = p.nslices;
     const uint64_t sell_entries = p.sell_entries;
     const bool c16 = p.c16, csr16 = p.csr16;
+    DevOwner &own = c->own;
+    SellDev &d = c->sell;
     c->rowsplit = p.rowsplit; c->fw = p.fw;
     c->sell_entries = sell_entries; c->sell_nnz = p.sell_nnz; c->sell_rows = p.sell_rows;
-    c->sell_jag = p.jag && sell_entries > 0;
+    d.jag = p.jag && sell_entries > 0 ? 1 : 0;
     c->uniform_entries = p.uniform_entries; c->constant_entries = p.constant_entries; c->masked_rows = p.masked_rows;
     c->n_int = (uint32_t)p.bint.size(); c->n_bnd = (uint32_t)p.bbnd.size();
     c->nblk = c->n_int + c->n_bnd;
@@ -644,69 +645,69 @@ static void sell_plan_upload(bicg_ctx *c, const CSR_Matrix *diag, const SellPlan
     c->glist_int_identity = c->ng_int == p.ngroups;     // every group, in order: index directly
     c->glist_all = c->ng_int + c->ng_bnd == p.ngroups;
     const bool need_csr = c->nblk > 0;
-    c->d_val = dev_upload_padded(diag->val, need_csr ? c->nnz_d : 0, kPadEntries);
-    c->d_col = dev_upload_padded(diag->col, need_csr && !csr16 ? c->nnz_d : 0, kPadEntries);
-    if (csr16) c->d_col16 = dev_upload(p.dcol16.data(), p.dcol16.size());
-    c->d_ptr = dev_upload(diag->ptr, (size_t)c->n_loc + 1);
-    c->o_val = dev_upload(h.oval.data(), c->nnz_o);
-    c->o_col = dev_upload(h.ocol.data(), c->nnz_o);
-    c->o_ptr = dev_upload(h.optr.data(), (size_t)c->n_loc + 1);
-    c->desc_int = dev_upload(p.bint.data(), p.bint.size());
-    c->desc_bnd = dev_upload(p.bbnd.data(), p.bbnd.size());
+    c->diag.val = own.upload_padded(diag->val, need_csr ? c->nnz_d : 0, kPadEntries);
+    c->diag.col = own.upload_padded(diag->col, need_csr && !csr16 ? c->nnz_d : 0, kPadEntries);
+    if (csr16) c->d_col16 = own.upload(p.dcol16.data(), p.dcol16.size());
+    c->diag.ptr = own.upload(diag->ptr, (size_t)c->n_loc + 1);
+    c->offd.val = own.upload(h.oval.data(), c->nnz_o);
+    c->offd.col = own.upload(h.ocol.data(), c->nnz_o);
+    c->offd.ptr = own.upload(h.optr.data(), (size_t)c->n_loc + 1);
+    c->desc_int = own.upload(p.bint.data(), p.bint.size());
+    c->desc_bnd = own.upload(p.bbnd.data(), p.bbnd.size());
     // (jagged slices: lanes whose row has ended read up to one entry past the last -- kPadEntries of slack)
-    c->s_val = dev_upload_padded(p.sval.get(), (size_t)sell_entries, kPadEntries);
-    c->s_col = dev_upload_padded(p.scol.get(), c16 ? 0 : (size_t)sell_entries, kPadEntries);
+    d.val = own.upload_padded(p.sval.get(), (size_t)sell_entries, kPadEntries);
+    d.col = own.upload_padded(p.scol.get(), c16 ? 0 : (size_t)sell_entries, kPadEntries);
     if (!p.vbase.empty()) {
-        c->s_vbase = dev_upload(p.vbase.data(), p.vbase.size());
-        c->s_uval = dev_upload(p.uval.data(), p.uval.size());
+        d.vbase = own.upload(p.vbase.data(), p.vbase.size());
+        d.uval = own.upload(p.uval.data(), p.uval.size());
     }
     if (!p.mbase.empty()) {
-        c->s_mbase = dev_upload(p.mbase.data(), p.mbase.size());
-        c->s_rmask = dev_upload(p.rmask.data(), p.rmask.size());
+        d.mbase = own.upload(p.mbase.data(), p.mbase.size());
+        d.rmask = own.upload(p.rmask.data(), p.rmask.size());
     }
     if (!p.ubase.empty()) {
-        c->s_ubase = dev_upload(p.ubase.data(), p.ubase.size());
-        c->s_uoff = dev_upload(p.uoff.data(), p.uoff.size());
+        d.ubase = own.upload(p.ubase.data(), p.ubase.size());
+        d.uoff = own.upload(p.uoff.data(), p.uoff.size());
     }
     build_slice_desc(c, nslices, nrows, p.slice_len.data(), p.ubase, p.vbase, p.mbase, p.uoff, p.uval, p.rmask.empty() ? nullptr : p.rmask.data());
     if (c16) {
-        c->s_col16 = dev_upload_padded(p.scol16.get(), p.n16_alloc(), kPadEntries);
-        c->s_base16 = dev_upload(p.slice_base16.data(), p.slice_base16.size());
+        d.col16 = own.upload_padded(p.scol16.get(), p.n16_alloc(), kPadEntries);
+        d.slice_base16 = own.upload(p.slice_base16.data(), p.slice_base16.size());
     }
     if (p.win) {
-        c->win_ptr = dev_upload(p.win_ptr.data(), p.win_ptr.size());
-        c->win_runs = dev_upload(p.win_runs.data(), p.win_runs.size());
-        c->win_slots = p.win_slots; c->win_max_runs = p.win_max_runs; c->win_near16 = p.win_near16;
+        d.win_ptr = own.upload(p.win_ptr.data(), p.win_ptr.size());
+        d.win_runs = own.upload(p.win_runs.data(), p.win_runs.size());
+        d.win_slots = p.win_slots; d.win_max_runs = p.win_max_runs; c->win_near16 = p.win_near16;
         if (p.win_list_mode) {
-            c->win_list = dev_upload(p.list.data(), p.list.size());
-            c->win_lptr = dev_upload(p.lptr.data(), p.lptr.size());
-            c->win_ltotal = dev_upload(p.total.data(), p.total.size());
+            d.win_list = own.upload(p.list.data(), p.list.size());
+            d.win_lptr = own.upload(p.lptr.data(), p.lptr.size());
+            d.win_ltotal = own.upload(p.total.data(), p.total.size());
         }
-        if (!p.perm.empty()) c->sell_perm = dev_upload(p.perm.data(), p.perm.size());
+        if (!p.perm.empty()) d.perm = own.upload(p.perm.data(), p.perm.size());
     }
     if (p.jag && sell_entries > 0) {
         c->jag_tail16_max = p.jag_tail16_max;
-        if (!p.lane_info.empty()) c->lane_info = dev_upload(p.lane_info.data(), p.lane_info.size());
+        if (!p.lane_info.empty()) d.lane_info = own.upload(p.lane_info.data(), p.lane_info.size());
         if (sw.jagw >= 0) c->jagw_fast = sw.jagw != 0;
     }
-    c->s_base = dev_upload(p.slice_base.data(), p.slice_base.size());
-    c->s_len = dev_upload(p.slice_len.data(), p.slice_len.size());
-    c->glist_int = dev_upload(p.gl_int.data(), p.gl_int.size());
-    c->glist_bnd = dev_upload(p.gl_bnd.data(), p.gl_bnd.size());
-    c->send_idx = dev_upload(h.send_idx.data(), c->nsend);
-    c->sendbuf = dev_alloc<double>(c->nsend);
+    d.slice_base = own.upload(p.slice_base.data(), p.slice_base.size());
+    d.slice_len = own.upload(p.slice_len.data(), p.slice_len.size());
+    c->glist_int = own.upload(p.gl_int.data(), p.gl_int.size());
+    c->glist_bnd = own.upload(p.gl_bnd.data(), p.gl_bnd.size());
+    c->send_idx = own.upload(h.send_idx.data(), c->nsend);
+    c->sendbuf = own.alloc<double>(c->nsend);
 
     // ---- bytes. matrix_bytes: what one SpMV streams from the matrix arrays; device_matrix_bytes: what is resident.
     const uint64_t ptr_bytes = 4ull * (nrows + 1);
     const uint64_t list_bytes = p.win && p.win_list_mode ? 4ull * p.list.size() + 8ull * p.lptr.size() : 0ull;
     const uint64_t run_bytes = p.win ? 4ull * p.win_ptr.size() + 8ull * p.win_runs.size() : 0ull;
-    const uint64_t lane_bytes = c->lane_info ? 2ull * p.lane_info.size() : 0ull;
+    const uint64_t lane_bytes = d.lane_info ? 2ull * p.lane_info.size() : 0ull;
     // (16 bytes of descriptor per slice where base + length were counted; the list-driven product reads the list, not the runs)
     const uint64_t streamed = (uint64_t)sell_entries * (c16 ? 10 : 12) - p.uniform_entries * (c16 ? 2 : 4) - p.constant_entries * 8ull + 2ull * p.masked_rows +
                               8ull * nslices + ptr_bytes + (uint64_t)(c->nnz_d - c->sell_nnz) * (csr16 ? 10 : 12) + (uint64_t)c->nnz_o * 12 +
-                              (c->s_desc ? 8ull * nslices : 0ull) + list_bytes + (p.win_list_mode ? 0ull : run_bytes) + lane_bytes;
+                              (d.sdesc ? 8ull * nslices : 0ull) + list_bytes + (p.win_list_mode ? 0ull : run_bytes) + lane_bytes;
     // (one rank: every product goes through the three-trip kernels, which do not read the row pointers)
-    c->matrix_bytes = streamed - (c->lane_info && c->nranks == 1 && streamed > ptr_bytes ? ptr_bytes : 0ull);
+    c->matrix_bytes = streamed - (d.lane_info && c->nranks == 1 && streamed > ptr_bytes ? ptr_bytes : 0ull);
     c->device_matrix_bytes = (need_csr ? (csr16 ? 10ull : 12ull) * c->nnz_d : 0ull) + 4ull * (c->n_loc + 1) + 12ull * c->nnz_o + 4ull * (c->n_loc + 1) +
                              8ull * sell_entries + (c16 ? 2ull * p.n16 : 4ull * sell_entries) + 12ull * nslices + list_bytes + run_bytes + lane_bytes;
 }
@@ -717,18 +718,19 @@ static void sell_plan_upload(bicg_ctx *c, const CSR_Matrix *diag, const SellPlan
 // others form one range of planes. (Collective.)
 static void stencil_across_ranks(bicg_ctx *c, Comm *comm, const std::vector<uint32_t> &gl_bnd)
 {
-    const uint32_t gpp = (c->st.on && c->st.sz % kGroupRows == 0) ? c->st.sz / kGroupRows : 0u;
-    std::vector<char> bnd_plane(c->st.on ? c->st.nz : 1u, 0);
+    StencilDev &st = c->sell.st;
+    const uint32_t gpp = (st.on && st.sz % kGroupRows == 0) ? st.sz / kGroupRows : 0u;
+    std::vector<char> bnd_plane(st.on ? st.nz : 1u, 0);
     bool ok = gpp > 0 && c->glist_all && c->nblk == 0;
     for (uint32_t g : gl_bnd) if (ok) bnd_plane[(size_t)g / gpp] = 1;
-    uint32_t nb = 0, lo = c->st.nz, hi = 0;
-    for (uint32_t z = 0; ok && z < c->st.nz; ++z) { if (bnd_plane[z]) ++nb; else { lo = std::min(lo, z); hi = std::max(hi, z + 1); } }
+    uint32_t nb = 0, lo = st.nz, hi = 0;
+    for (uint32_t z = 0; ok && z < st.nz; ++z) { if (bnd_plane[z]) ++nb; else { lo = std::min(lo, z); hi = std::max(hi, z + 1); } }
     ok = ok && (uint64_t)nb * gpp == gl_bnd.size() && lo < hi;
     for (uint32_t z = lo; ok && z < hi; ++z) ok = !bnd_plane[z];
     ok = all_ranks(comm, ok);       // (every rank takes the same form of the exchange: collective)
-    if (ok) { c->st.z_lo = lo; c->st.z_hi = hi; c->st_multi = true; }
+    if (ok) { st.z_lo = lo; st.z_hi = hi; c->st_multi = true; }
     if (plan_trace_env() && c->rank == 0)
-        fprintf(stderr, "bicgstab_hip: plane-marching product across ranks: %s (planes %u .. %u of %u without halo entries)\n", ok ? "yes" : "no", lo, hi, c->st.nz);
+        fprintf(stderr, "bicgstab_hip: plane-marching product across ranks: %s (planes %u .. %u of %u without halo entries)\n", ok ? "yes" : "no", lo, hi, st.nz);
 }
 
 // ---- peer-to-peer transport: publish this rank's halo landing ring, learn where every entry
@@ -763,20 +765,20 @@ static void p2p_transport(bicg_ctx *c, Comm *comm, const SellPlan &plan, HaloHos
             h.dst0[i] = (unsigned long long)(uintptr_t)rings[p] + 16ull * ((unsigned long long)theirs[2 * p] + j);
             h.dstride[i] = 16ull * (unsigned long long)theirs[2 * p + 1];
         }
-    c->push_dst0 = dev_upload(h.dst0.data(), h.dst0.size());
-    c->push_stride = dev_upload(h.dstride.data(), h.dstride.size());
+    c->push_dst0 = c->own.upload(h.dst0.data(), h.dst0.size());
+    c->push_stride = c->own.upload(h.dstride.data(), h.dstride.size());
     c->ll_fused = c->n_bnd == 0 && c->ng_int + c->ng_bnd > 0;
     // Ragged rows (jagged slices): the launch with the exchange inside runs k_spmv_sell's loop over EVERY group, the rank's
     // halo-free groups included; as separate launches -- push, interior, unpack, boundary -- the interior goes through the
     // three-trip products of bicg_jagw.hip. Worth two more launches when the interior is large (measured with two 800 k-row
     // ranks of the RCM-numbered mesh matrix sharing a GPU: profiles/r06/ragged_ranks_fused_or_split.txt); BICG_PLAN="halo-fused=0|1" decides.
-    if (c->ll_fused && c->sell_jag && c->lane_info && c->jagw_fast && (uint64_t)c->nnz_d >= 4000000ull) c->ll_fused = false;
+    if (c->ll_fused && c->sell.jag && c->sell.lane_info && c->jagw_fast && (uint64_t)c->nnz_d >= 4000000ull) c->ll_fused = false;
     if (const char *sv = plan_tok("halo-fused")) c->ll_fused = c->n_bnd == 0 && c->ng_int + c->ng_bnd > 0 && atoi(sv) != 0;
     if (const char *sv = knob_x("BICG_P2P_FUSED")) c->ll_fused = c->ll_fused && atoi(sv) != 0;
     if (c->ll_fused) {
         std::vector<uint32_t> order(plan.gl_int);
         order.insert(order.end(), plan.gl_bnd.begin(), plan.gl_bnd.end());
-        c->glist_ll = dev_upload(order.data(), order.size());
+        c->glist_ll = c->own.upload(order.data(), order.size());
     }
 }
 
@@ -885,7 +887,7 @@ bicg_ctx *bicg_create_device_csr(const double *val_d, const unsigned int *col_d,
     else if (longest > std::max<uint64_t>(64, 4 * (uint64_t)nnz / rows)) why = "a row much longer than the average";
     if (why) {
         fprintf(stderr, "bicgstab_hip: bicg_create_device_csr: %s -- use bicg_create\n", why);
-        BICG_HIP(hipFree(slen_d)); BICG_HIP(hipFree(far_d));
+        dev_free(slen_d); dev_free(far_d);
         return nullptr;
     }
     bicg_ctx *c = new bicg_ctx;
@@ -897,34 +899,41 @@ bicg_ctx *bicg_create_device_csr(const double *val_d, const unsigned int *col_d,
     if (c->reorder_mode) fprintf(stderr, "bicgstab_hip: BICG_PLAN reorder=%d not taken (bicg_create_device_csr plans on the device; the host plan of bicg_create reorders)\n", c->reorder_mode);
     c->overlap = nnz >= 6000000u; c->fuse_small = nnz < 6000000u;
     c->scnt.assign(1, 0); c->sdsp.assign(1, 0); c->rcnt.assign(1, 0); c->rdsp.assign(1, 0);
-    c->sell_entries = entries; c->sell_nnz = nnz; c->sell_rows = rows; c->sell_jag = false;
-    c->s_val = dev_alloc<double>((size_t)entries + kPadEntries);
-    BICG_HIP(hipMemset(c->s_val, 0, sizeof(double) * ((size_t)entries + kPadEntries)));
+    c->sell_entries = entries; c->sell_nnz = nnz; c->sell_rows = rows;
+    // (what the set-up kernels write is built through these local pointers and published in c->sell when it is complete)
+    DevOwner &own = c->own;
+    SellDev &d = c->sell;
+    double *sval = own.alloc<double>((size_t)entries + kPadEntries);
+    BICG_HIP(hipMemset(sval, 0, sizeof(double) * ((size_t)entries + kPadEntries)));
+    uint32_t *scol = nullptr;
+    short *scol16 = nullptr;
     if (c16) {
-        c->s_col16 = dev_alloc<short>((size_t)n16 + kPadEntries);
-        BICG_HIP(hipMemset(c->s_col16, 0, sizeof(short) * ((size_t)n16 + kPadEntries)));
-        c->s_base16 = dev_upload(sbase16.data(), sbase16.size());
-        c->s_col = dev_alloc<uint32_t>(kPadEntries);
+        scol16 = own.alloc<short>((size_t)n16 + kPadEntries);
+        BICG_HIP(hipMemset(scol16, 0, sizeof(short) * ((size_t)n16 + kPadEntries)));
+        d.slice_base16 = own.upload(sbase16.data(), sbase16.size());
+        scol = own.alloc<uint32_t>(kPadEntries);
     } else {
-        c->s_col = dev_alloc<uint32_t>((size_t)entries + kPadEntries);
-        BICG_HIP(hipMemset(c->s_col, 0, sizeof(uint32_t) * ((size_t)entries + kPadEntries)));
+        scol = own.alloc<uint32_t>((size_t)entries + kPadEntries);
+        BICG_HIP(hipMemset(scol, 0, sizeof(uint32_t) * ((size_t)entries + kPadEntries)));
     }
-    c->s_base = dev_upload(sbase.data(), sbase.size());
-    c->s_len = slen_d;
-    launch_plan_fill(ptr_d, col_d, val_d, rows, c->s_base, c->s_base16, c->s_val, c16 ? nullptr : c->s_col, c16 ? c->s_col16 : nullptr, nullptr);
+    d.slice_base = own.upload(sbase.data(), sbase.size());
+    d.slice_len = own.adopt(slen_d);
+    launch_plan_fill(ptr_d, col_d, val_d, rows, d.slice_base, d.slice_base16, sval, c16 ? nullptr : scol, c16 ? scol16 : nullptr, nullptr);
+    d.val = sval; d.col = scol; d.col16 = scol16;
     // uniform slices (SellDev::ubase): found by a kernel, grouped by the hash of their distance lists here; one list per group
     // is fetched from the CSR (a stencil has a few dozen)
     uint64_t uniform_entries = 0, constant_entries = 0;
     uint32_t far_rows = 0;
     if (!plan_off("uniform")) {
         const bool want_constant = !plan_off("constant");
+        uint32_t *ubase_d = nullptr, *vbase_d = nullptr, *mbase_d = nullptr;      // (rewritten after launch_plan_verify where hashes collided)
         unsigned long long *uh_d = dev_alloc<unsigned long long>(2 * (size_t)nslices), *vh_d = uh_d + nslices;
         BICG_HIP(hipMemset(uh_d, 0, sizeof(unsigned long long) * 2 * (size_t)nslices));
         launch_plan_uniform(ptr_d, col_d, val_d, rows, uh_d, want_constant ? vh_d : nullptr, nullptr);
         std::vector<unsigned long long> uh(nslices), vh(nslices);
         BICG_HIP(hipMemcpy(uh.data(), uh_d, sizeof(unsigned long long) * nslices, hipMemcpyDeviceToHost));
         BICG_HIP(hipMemcpy(vh.data(), vh_d, sizeof(unsigned long long) * nslices, hipMemcpyDeviceToHost));
-        BICG_HIP(hipFree(uh_d));
+        dev_free(uh_d);
         // tests: every hash lands in one of TWO buckets -- slices with different lists collide in their thousands and
         // k_plan_verify has to catch each one (tests/test_full_size.py::test_device_plan_survives_hash_collisions)
         const bool collide = test_tok("plan-collide") != nullptr;
@@ -979,7 +988,7 @@ bicg_ctx *bicg_create_device_csr(const double *val_d, const unsigned int *col_d,
             launch_plan_masked(ptr_d, col_d, val_d, rows, mh_d, nullptr, nullptr, nullptr);
             std::vector<unsigned long long> mh(nslices);
             BICG_HIP(hipMemcpy(mh.data(), mh_d, sizeof(unsigned long long) * nslices, hipMemcpyDeviceToHost));
-            BICG_HIP(hipFree(mh_d));
+            dev_free(mh_d);
             if (collide) for (uint32_t sl = 0; sl < nslices; ++sl) if (mh[sl]) mh[sl] = (mh[sl] & 31ull) | (32ull << (mh[sl] >> 63));
             std::map<unsigned long long, std::pair<uint32_t, uint32_t>> mlists;       // hash -> (position in uoff, position in uval)
             std::vector<uint32_t> rp(kSliceRows + 1), rc;
@@ -1013,21 +1022,22 @@ bicg_ctx *bicg_create_device_csr(const double *val_d, const unsigned int *col_d,
                 uniform_entries += (uint64_t)slen[sl] * kSliceRows; constant_entries += (uint64_t)slen[sl] * kSliceRows;
             }
             if (nmasked) {
-                c->s_mbase = dev_upload(mbase.data(), mbase.size());
-                c->s_rmask = dev_alloc<unsigned short>((size_t)nmasked * kSliceRows);
-                BICG_HIP(hipMemset(c->s_rmask, 0, sizeof(unsigned short) * (size_t)nmasked * kSliceRows));
-                launch_plan_masked(ptr_d, col_d, val_d, rows, nullptr, c->s_mbase, c->s_rmask, nullptr);
+                mbase_d = own.upload(mbase.data(), mbase.size());
+                unsigned short *rmask = own.alloc<unsigned short>((size_t)nmasked * kSliceRows);
+                BICG_HIP(hipMemset(rmask, 0, sizeof(unsigned short) * (size_t)nmasked * kSliceRows));
+                launch_plan_masked(ptr_d, col_d, val_d, rows, nullptr, mbase_d, rmask, nullptr);
                 BICG_HIP(hipDeviceSynchronize());
+                d.rmask = rmask;
                 c->masked_rows = (uint64_t)nmasked * kSliceRows;
             }
         }
         if (uniform_entries) {
-            c->s_ubase = dev_upload(ubase.data(), ubase.size());
-            c->s_uoff = dev_upload(uoff.data(), uoff.size());
+            ubase_d = own.upload(ubase.data(), ubase.size());
+            d.uoff = own.upload(uoff.data(), uoff.size());
         }
         if (constant_entries) {
-            c->s_vbase = dev_upload(vbase.data(), vbase.size());
-            c->s_uval = dev_upload(uval.data(), uval.size());
+            vbase_d = own.upload(vbase.data(), vbase.size());
+            d.uval = own.upload(uval.data(), uval.size());
         }
         // The groups above are keyed by 64-bit hashes: every list-driven slice is now compared with the list it was given
         // (k_plan_verify), and a slice that differs -- a collision -- goes back to its stored columns and values, which
@@ -1035,10 +1045,10 @@ bicg_ctx *bicg_create_device_csr(const double *val_d, const unsigned int *col_d,
         if (uniform_entries) {
             unsigned char *bad_d = dev_alloc<unsigned char>(nslices);
             BICG_HIP(hipMemset(bad_d, 0, nslices));
-            launch_plan_verify(ptr_d, col_d, val_d, rows, slen_d, c->s_ubase, c->s_vbase, c->s_mbase, c->s_rmask, c->s_uoff, c->s_uval, bad_d, nullptr);
+            launch_plan_verify(ptr_d, col_d, val_d, rows, slen_d, ubase_d, vbase_d, mbase_d, d.rmask, d.uoff, d.uval, bad_d, nullptr);
             std::vector<unsigned char> bad(nslices);
             BICG_HIP(hipMemcpy(bad.data(), bad_d, nslices, hipMemcpyDeviceToHost));
-            BICG_HIP(hipFree(bad_d));
+            dev_free(bad_d);
             uint32_t nbad = 0;
             for (uint32_t sl = 0; sl < nslices; ++sl) {
                 if (!bad[sl]) continue;
@@ -1051,33 +1061,35 @@ bicg_ctx *bicg_create_device_csr(const double *val_d, const unsigned int *col_d,
             }
             c->plan_collisions = nbad;
             if (nbad) {
-                BICG_HIP(hipMemcpy(c->s_ubase, ubase.data(), sizeof(uint32_t) * nslices, hipMemcpyHostToDevice));
-                if (c->s_vbase) BICG_HIP(hipMemcpy(c->s_vbase, vbase.data(), sizeof(uint32_t) * nslices, hipMemcpyHostToDevice));
-                if (c->s_mbase) BICG_HIP(hipMemcpy(c->s_mbase, mbase.data(), sizeof(uint32_t) * nslices, hipMemcpyHostToDevice));
+                BICG_HIP(hipMemcpy(ubase_d, ubase.data(), sizeof(uint32_t) * nslices, hipMemcpyHostToDevice));
+                if (vbase_d) BICG_HIP(hipMemcpy(vbase_d, vbase.data(), sizeof(uint32_t) * nslices, hipMemcpyHostToDevice));
+                if (mbase_d) BICG_HIP(hipMemcpy(mbase_d, mbase.data(), sizeof(uint32_t) * nslices, hipMemcpyHostToDevice));
                 if (plan_trace_env()) fprintf(stderr, "bicgstab_hip: %u list-driven slices did not match their list (hash collision): stored as general slices\n", nbad);
             }
         }
+        d.ubase = ubase_d; d.vbase = vbase_d; d.mbase = mbase_d;
         if (constant_entries) build_slice_desc(c, nslices, rows, slen.data(), ubase, vbase, mbase, uoff, uval, nullptr);
     }
     c->uniform_entries = uniform_entries;
     c->constant_entries = constant_entries;
     c->far_rows = far_rows;
-    c->d_ptr = dev_alloc<uint32_t>((size_t)rows + 1);
-    BICG_HIP(hipMemcpy(c->d_ptr, ptr_d, sizeof(uint32_t) * ((size_t)rows + 1), hipMemcpyDeviceToDevice));
-    c->d_val = dev_alloc<double>(kPadEntries); c->d_col = dev_alloc<uint32_t>(kPadEntries);
-    c->o_val = dev_alloc<double>(1); c->o_col = dev_alloc<uint32_t>(1);
-    c->o_ptr = dev_alloc<uint32_t>((size_t)rows + 1);
-    BICG_HIP(hipMemset(c->o_ptr, 0, sizeof(uint32_t) * ((size_t)rows + 1)));
-    c->desc_int = dev_alloc<uint4>(1); c->desc_bnd = dev_alloc<uint4>(1);
-    c->glist_int = dev_alloc<uint32_t>(1); c->glist_bnd = dev_alloc<uint32_t>(1);
-    c->send_idx = dev_alloc<uint32_t>(1); c->sendbuf = dev_alloc<double>(1);
+    uint32_t *dptr = own.alloc<uint32_t>((size_t)rows + 1);
+    BICG_HIP(hipMemcpy(dptr, ptr_d, sizeof(uint32_t) * ((size_t)rows + 1), hipMemcpyDeviceToDevice));
+    c->diag = {own.alloc<double>(kPadEntries), own.alloc<uint32_t>(kPadEntries), dptr};
+    double *oval = own.alloc<double>(1);
+    uint32_t *ocol = own.alloc<uint32_t>(1), *optr = own.alloc<uint32_t>((size_t)rows + 1);
+    BICG_HIP(hipMemset(optr, 0, sizeof(uint32_t) * ((size_t)rows + 1)));
+    c->offd = {oval, ocol, optr};
+    c->desc_int = own.alloc<uint4>(1); c->desc_bnd = own.alloc<uint4>(1);
+    c->glist_int = own.alloc<uint32_t>(1); c->glist_bnd = own.alloc<uint32_t>(1);
+    c->send_idx = own.alloc<uint32_t>(1); c->sendbuf = own.alloc<double>(1);
     c->ng_int = ngroups; c->ng_bnd = 0; c->n_int = c->n_bnd = c->nblk = 0;
     c->glist_int_identity = true; c->glist_all = true;
     sell_order_for_big_grids(c, ngroups);
     c->matrix_bytes = entries * (c16 ? 10 : 12) - uniform_entries * (c16 ? 2 : 4) - constant_entries * 8ull + 2ull * c->masked_rows + 8ull * nslices + 4ull * ((uint64_t)rows + 1);
-    if (c->s_desc) c->matrix_bytes += 8ull * nslices;
+    if (d.sdesc) c->matrix_bytes += 8ull * nslices;
     c->device_matrix_bytes = 8ull * ((uint64_t)rows + 1) + 8ull * entries + (c16 ? 2ull * n16 : 4ull * entries) + 12ull * nslices;
-    BICG_HIP(hipFree(far_d));
+    dev_free(far_d);
     PlanTrace quiet;
     ctx_finish(c, comm, ngroups, nullptr, nullptr, quiet);
     if (plan_seconds) *plan_seconds = now_sec() - t0;
@@ -1111,16 +1123,9 @@ void bicg_destroy(bicg_ctx *c)
     g_live.erase(std::remove(g_live.begin(), g_live.end(), c), g_live.end());
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    void *ptrs[] = {c->d_val, c->d_col, c->d_ptr, c->o_val, c->o_col, c->o_ptr, c->desc_int, c->desc_bnd, c->s_val, c->s_col, c->s_base, c->s_len, c->s_col16, c->s_base16, c->s_ubase, c->s_uoff, c->s_vbase, c->s_uval, c->s_mbase, c->s_rmask, c->s_desc, c->s_uoff8, c->st_code, c->st_tab, c->st_cmask, c->st_wbits, c->d_col16, c->win_ptr, c->win_runs, c->win_list, c->win_lptr, c->win_ltotal, c->sell_perm, c->lane_info, c->waitlog, c->sh_dev, c->sh_arrays, c->p_set, c->x_set, c->glist_int, c->glist_bnd,
-                    c->send_idx, c->sendbuf, c->slab, c->partial, c->shard_tot, c->counter, c->Sbuf, c->trace, c->sw_buf,
-                    c->wpart[0], c->wpart[1], c->shard_ll, c->tail_tab, c->tail_shard, c->hand_shard, c->alarm, c->mm_in, c->mm_xt, c->mm_yt, c->mm_part, c->mm_out, c->mm_sigma, c->set_send, c->set_recv, c->set_smap, c->set_rmap, c->ro_perm, c->ro_inv, c->ro_stage};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (void *p : c->persist_mem) if (p) (void)hipFree(p);
-    multi_release(c);
+    c->own.clear();
+    c->persist_own.clear();
     release_p2p(c);
-    if (c->push_dst0) (void)hipFree(c->push_dst0);
-    if (c->push_stride) (void)hipFree(c->push_stride);
-    if (c->glist_ll) (void)hipFree(c->glist_ll);
     if (c->hS) (void)hipHostFree(c->hS);
     if (c->h_alarm) (void)hipHostFree(c->h_alarm);
     for (int i = 0; i < kEvRing; ++i) {

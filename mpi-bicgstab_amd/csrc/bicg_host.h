@@ -1,15 +1,17 @@
-// bicg_host.h -- what the host-side translation units of the library share: the context of a rank (struct bicg_ctx), small
-// device-memory helpers, section timing, and the prototypes of the functions that cross file boundaries.
+// bicg_host.h -- what the host-side translation units of the library share: the context of a rank (struct bicg_ctx), the
+// device-memory helpers and their owner (dev_alloc / dev_free, struct DevOwner), section timing, and the prototypes of the functions that cross file boundaries.
 //   bicg_solver.cpp   dot groups, the distributed SpMV, the four iterations of reference src/solver.c, run_begin / iterate / end
 //   bicg_shifted.cpp  the shifted family (src/shifted_solver.c, src/shifted_switching_solver.c) and its section prints
 //   bicg_multi.cpp    bicg_solve_multi: plain BiCGStab on up to kSpmmCols right-hand sides per pass over the matrix
 //   bicg_create.cpp   bicg_create / bicg_create_device_csr: halo plan, upload of the diag block's plan (made by bicg_sell_plan.cpp,
-//                     host only: bicg_plan.h), slice descriptors, stencil plan, transport, persistent set-up, destroy
+//                     host only: bicg_plan.h) into bicg_ctx::sell / diag / offd, slice descriptors, stencil plan, transport,
+//                     persistent set-up, destroy (clears the context's DevOwner: the one owner of its device memory)
 //   bicg_dropin.cpp   the reference's own symbols (solver.h, shifted_solver.h, shifted_switching_solver.h), matrix residency
 //   bicg_api.cpp      the additive handle API (load / fetch / spmv / dot / spmm / info calls)
 #pragma once
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -39,10 +41,18 @@ inline double now_sec()
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// device allocations made through the helpers below and not yet freed, in this process (bicg_device_allocations)
+inline std::atomic<long long> &dev_live()
+{
+    static std::atomic<long long> n{0};
+    return n;
+}
+
 template <class T> T *dev_alloc(size_t n)
 {
     T *p = nullptr;
     BICG_HIP(hipMalloc((void **)&p, sizeof(T) * (n ? n : 1)));
+    ++dev_live();
     return p;
 }
 
@@ -62,6 +72,37 @@ template <class T> T *dev_upload_padded(const T *src, size_t n, size_t pad)
     return p;
 }
 
+// the counterpart of the three helpers above (a temporary of one function); null: nothing. checked = false: on the way out
+// after a failure or at tear-down, where an error of the device is not news
+inline void dev_free(const void *p, bool checked = true)
+{
+    if (!p) return;
+    if (checked) BICG_HIP(hipFree(const_cast<void *>(p)));
+    else (void)hipFree(const_cast<void *>(p));
+    --dev_live();
+}
+
+// Device memory that lives as long as its holder: whatever is allocated through an owner is freed by clear() (bicg_destroy), so
+// a buffer added to the context cannot be left off a list. free / regrow are for the buffers that grow with the largest call.
+struct DevOwner {
+    std::vector<void *> ptrs;
+    template <class T> T *adopt(T *p) { ptrs.push_back((void *)p); return p; }      // a dev_alloc made before the holder existed
+    template <class T> T *alloc(size_t n) { return adopt(dev_alloc<T>(n)); }
+    template <class T> T *upload(const T *src, size_t n) { return adopt(dev_upload(src, n)); }
+    template <class T> T *upload_padded(const T *src, size_t n, size_t pad) { return adopt(dev_upload_padded(src, n, pad)); }
+    void free(const void *p)
+    {
+        if (!p) return;
+        ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), (void *)p), ptrs.end());
+        dev_free(p);
+    }
+    template <class T> T *regrow(T *p, size_t n) { free(p); return alloc<T>(n); }
+    void clear()
+    {
+        for (void *p : ptrs) dev_free(p, false);
+        ptrs.clear();
+    }
+};
 
 constexpr unsigned kWaitCap = 4096;      // samples per row of PersistArgs::waitlog
 struct bicg_ctx {
@@ -70,9 +111,14 @@ struct bicg_ctx {
     int nranks = 1, rank = 0;
     uint32_t n_loc = 0, n_glob = 0, halo = 0, stride = 0, nnz_d = 0, nnz_o = 0;
 
-    // matrix + plan (device)
-    double *d_val = nullptr, *o_val = nullptr;
-    uint32_t *d_col = nullptr, *d_ptr = nullptr, *o_col = nullptr, *o_ptr = nullptr;
+    // Device memory of the context's lifetime: every allocation goes through `own` (the persistent plan's through `persist_own`,
+    // which ctx_finish drops as a whole when the ranks do not agree on it); bicg_destroy clears both. Outside them: the landing
+    // ring (the transport's shared memory, release_p2p), the pinned host blocks, events, streams, graphs.
+    DevOwner own, persist_own;
+    // matrix + plan (device): the structs the product kernels take, filled once by set-up (sell_plan_upload, build_slice_desc,
+    // build_stencil_plan, stencil_across_ranks, bicg_create_device_csr) and copied into every launch's arguments
+    SellDev sell{};                        // sliced-ELL copy of the diag block (rows whose 256-row group pads by < 25 %)
+    CsrDev diag{}, offd{};                 // CSR blocks: local columns / columns renumbered to rows + halo position
     uint4 *desc_int = nullptr, *desc_bnd = nullptr;   // CSR row-block descriptors: interior / halo-touching
     FusedWindow fw{};                      // clusters of column distances of a padded 16-bit block (fw.ncl > 0): the windows of the SpMM kernels
     bool rowsplit = false;                 // long rows: the row blocks go to k_spmv_rows (a row spread over T lanes)
@@ -91,39 +137,19 @@ struct bicg_ctx {
     unsigned *waitlog = nullptr;           // PersistArgs::waitlog (multi-rank persistent launches), 3 rows of kWaitCap samples
     double t_enq = 0.0;
     uint64_t device_matrix_bytes = 0;      // bytes of matrix storage resident on the GPU
-    // sliced-ELL copy of the diag block (rows whose 256-row group pads by < 25 %)
-    double *s_val = nullptr;
-    uint32_t *s_col = nullptr, *s_base = nullptr, *s_len = nullptr, *s_base16 = nullptr;
-    short *s_col16 = nullptr;
-    uint32_t *s_ubase = nullptr;           // uniform slices (SellDev::ubase / uoff): BICG_PLAN="uniform=0" switches them off
-    int *s_uoff = nullptr;
-    uint64_t uniform_entries = 0;          // sliced-ELL entries whose columns the SpMV does not read
+    // host-side facts of the plan (BICG_PLAN="uniform=0" / "constant=0" / "masked=0" / "desc=0" / "lists=0" / "stencil=0" switch
+    // the matching SellDev members off)
+    uint64_t uniform_entries = 0;          // sliced-ELL entries whose columns the SpMV does not read (SellDev::ubase / uoff)
     uint32_t far_rows = 0;                 // farthest column distance of a uniform slice, in rows (a grid's plane size)
-    uint32_t *s_mbase = nullptr;           // masked slices (SellDev::mbase / rmask): BICG_PLAN="masked=0" switches them off
-    unsigned short *s_rmask = nullptr;
-    uint64_t masked_rows = 0;
+    uint64_t masked_rows = 0;              // rows of masked slices (SellDev::mbase / rmask)
     uint32_t plan_collisions = 0;          // list-driven slices the device plan's verification pass put back (bicg_plan_collisions)
-    int *s_uoff8 = nullptr;                // SellDev::uoff8
-    int sell_ystride = 0;                  // SellDev::ystride (BICG_SELL_YGROUP=1; default: consecutive slices per workgroup)
-    bool sell_all_lists = false;           // SellDev::all_lists (BICG_PLAN="lists=0" switches the loop of its own off)
-    StencilDev st{};                       // SellDev::st: the plane-marching product of a 7-point grid stencil (BICG_PLAN="stencil=0": off)
-    uint32_t *st_code = nullptr; StencilTab *st_tab = nullptr; unsigned char *st_cmask = nullptr; uint32_t *st_wbits = nullptr;
     bool st_multi = false;                 // several ranks: the halo-free rows of this rank are the whole planes z_lo .. z_hi - 1 of its grid
     bool ca_fuse = true;                   // CA-BiCGStab: q, y and their dots in the epilogue of z = A s (plane-marching product only; BICG_PLAN="ca-fuse=0")
-    uint4 *s_desc = nullptr;               // one descriptor per slice (SellDev::sdesc): BICG_PLAN="desc=0" switches them off
-    uint32_t *s_vbase = nullptr;           // constant slices (SellDev::vbase / uval): BICG_PLAN="constant=0" switches them off
-    double *s_uval = nullptr;
-    uint64_t constant_entries = 0;         // ... whose values it does not read either
-    bool sell_jag = false;                 // jagged slices (ragged rows: no padding stored), SellDev::jag
-    uint32_t *win_ptr = nullptr, win_slots = 0;   // x windows in LDS (SellDev::win_*)
-    uint32_t win_max_runs = 0;             // most runs of one group's window
+    uint64_t constant_entries = 0;         // ... whose values it does not read either (SellDev::vbase / uval)
     uint32_t jag_tail16_max = 0;           // most entries one jagged slice holds behind the 16th entry of its rows
     bool win_near16 = false;               // every window column lies within 16 bits of its group's first row (k_spmm_jpipe packs them)
-    uint2 *win_runs = nullptr;
-    unsigned char *sell_perm = nullptr;    // SellDev::perm
-    unsigned short *lane_info = nullptr;   // SellDev::lane_info
-    uint32_t *win_list = nullptr, *win_lptr = nullptr, *win_ltotal = nullptr;     // list-driven window (SellDev::win_list)
-    bool jagw_fast = true;                 // the three-trip product of bicg_jagw.hip (BICG_PLAN="jagw=0": k_spmv_sell's loop)
+    bool jagw_fast = true;                 // the three-trip product of bicg_jagw.hip (BICG_PLAN="jagw=0": k_spmv_sell's loop, which
+                                           // spmv() selects by passing SellDev::lane_info as null)
     uint32_t *glist_int = nullptr, *glist_bnd = nullptr;
     uint32_t ng_int = 0, ng_bnd = 0, sell_rows = 0;
     uint64_t sell_entries = 0, sell_nnz = 0;
@@ -192,7 +218,6 @@ struct bicg_ctx {
     bool last_shifted_persist = false;   // the last shifted solve ran as persistent launches (bicg_result.flags of bicg_solve_shifted)
     unsigned persist_seq = 0;    // LL tags used so far (dot tables)
     unsigned persist_vseq = 0;   // ... by the pipelined kernel's vector images
-    std::vector<void *> persist_mem;
     unsigned wg_cap = 0;         // ranks sharing this GPU (tests): workgroups per launch that may wait for another rank
     double *wpart[2] = {nullptr, nullptr};   // per-wavefront partial sums, alternating between groups
     llword *shard_ll = nullptr;  // 2 x [kShards][kRedSlots][2], alternating like wpart
@@ -459,8 +484,6 @@ int run_solver(bicg_ctx *c, int method, const bicg_options *opt_in, bicg_result 
 // ---- the shifted family (bicg_shifted.cpp)
 int run_shifted(bicg_ctx *c, int mode, double *x_set_host, double *r_host, const double *sigma, int nsig, int seed,
                 const bicg_options *opt_in, bicg_result *res);
-// ---- multi-RHS BiCGStab (bicg_multi.cpp)
-void multi_release(bicg_ctx *c);
 // ---- plan and context (bicg_create.cpp)
 bool all_ranks(Comm *comm, bool mine);
 void sell_order_for_big_grids(bicg_ctx *c, uint32_t ngroups);

@@ -25,9 +25,9 @@ void multi_buffers(bicg_ctx *c)
     const size_t st = c->stride;
     // (+64: k_spmm_pipe copies 16-byte pairs, the last one may reach one column past a vector -- as for mm_in, spmm_buffers)
     const size_t slab = 6 * (size_t)kSpmmCols * st + 64;
-    c->mt_slab = dev_alloc<double>(slab);
-    c->mt_part = dev_alloc<double>(2 * (size_t)kSpmmCols * multi_grid(c->n_loc));
-    c->mt_S = dev_alloc<MultiScal>(1);
+    c->mt_slab = c->own.alloc<double>(slab);
+    c->mt_part = c->own.alloc<double>(2 * (size_t)kSpmmCols * multi_grid(c->n_loc));
+    c->mt_S = c->own.alloc<MultiScal>(1);
     BICG_HIP(hipMemset(c->mt_slab, 0, sizeof(double) * slab));      // padding rows and unused columns stay finite
     BICG_HIP(hipDeviceSynchronize());      // the memset ran on the null stream: c->sc does not wait for it
 }
@@ -64,7 +64,7 @@ constexpr int kRedRow = 2 * kSpmmCols;      // doubles per rank in mt_red
 
 void multi_red_buffer(bicg_ctx *c)
 {
-    if (!c->mt_red) c->mt_red = dev_alloc<double>((size_t)c->nranks * kRedRow);
+    if (!c->mt_red) c->mt_red = c->own.alloc<double>((size_t)c->nranks * kRedRow);
 }
 
 // the dot group `phase` of a set: one rank -> k_multi_finish; several -> local sums, one gathering all-reduce, apply
@@ -101,13 +101,6 @@ bool multi_agree(bicg_ctx *c, int method, int nrhs, const bicg_options &o, bool 
 
 }  // namespace
 
-void multi_release(bicg_ctx *c)
-{
-    for (void *p : {(void *)c->mt_slab, (void *)c->mt_part, (void *)c->mt_trace, (void *)c->mt_S, (void *)c->mt_red})
-        if (p) (void)hipFree(p);
-    c->mt_slab = c->mt_part = c->mt_trace = c->mt_red = nullptr; c->mt_S = nullptr;
-}
-
 extern "C" {
 
 int bicg_solve_multi(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_set, int nrhs, const bicg_options *opt_in,
@@ -135,9 +128,8 @@ int bicg_solve_multi(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_s
     multi_buffers(c);
     const bool tracing = o.record_trace != 0 && o.max_iter > 0;
     if (tracing && c->mt_trace_cap < o.max_iter) {
-        if (c->mt_trace) BICG_HIP(hipFree(c->mt_trace));
         c->mt_trace_cap = o.max_iter;
-        c->mt_trace = dev_alloc<double>(4 * (size_t)kSpmmCols * c->mt_trace_cap);
+        c->mt_trace = c->own.regrow(c->mt_trace, 4 * (size_t)kSpmmCols * c->mt_trace_cap);
     }
     c->mt_host_trace.clear(); c->mt_iters.clear();
     if (tracing) { c->mt_host_trace.resize((size_t)nrhs); c->mt_iters.assign((size_t)nrhs, 0); }

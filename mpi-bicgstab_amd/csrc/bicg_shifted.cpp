@@ -68,6 +68,65 @@ void print_section_table(bicg_ctx *c, int its, int nsig, const int *unsolved, do
     printf("Switch time  : %e [sec.]\n", c->switch_sec);
 }
 
+// The set-up the entry points of the family share: the per-shift buffers grown to nsig shifts, ShiftDev laid out over them and
+// uploaded, sigma, zeroed sets (calloc, src/shifted_solver.c:223), the caller's x set and r, the trace grown to max_iter, the
+// scalar block, zeroed counters and work vectors, section timing. arc_len > 0 (the seed-switching variants): the archives of
+// arc_len entries (doubles) followed by the flag arrays, in sw_buf. Returns ShiftDev as the device holds it.
+static ShiftDev shifted_setup(bicg_ctx *c, int mode, const double *x_set_host, const double *r_host, const double *sigma, int nsig, int seed,
+                              const bicg_options &o, int arc_len)
+{
+    const size_t st = c->stride, L = (size_t)arc_len;
+    if (c->sh_cap < nsig) {
+        for (void *p : {(void *)c->sh_dev, (void *)c->sh_arrays, (void *)c->p_set, (void *)c->x_set}) c->own.free(p);
+        c->sh_dev = c->own.alloc<ShiftDev>(1);
+        c->sh_arrays = c->own.alloc<double>(12 * (size_t)nsig);
+        c->p_set = c->own.alloc<double>((size_t)nsig * st);
+        c->x_set = c->own.alloc<double>((size_t)nsig * st);
+        c->sh_cap = nsig;
+    }
+    const size_t nd = 3 * L + (size_t)nsig * L, ni = 2 * (size_t)nsig + L;     // (+ the systems still running, per iteration)
+    const size_t need = nd * sizeof(double) + ni * sizeof(int);
+    if (arc_len && c->sw_cap < need) {
+        c->sw_buf = c->own.regrow(c->sw_buf, (need + sizeof(double) - 1) / sizeof(double));
+        c->sw_cap = need;
+    }
+    ShiftDev h;
+    memset(&h, 0, sizeof h);
+    h.nsig = nsig; h.seed = seed; h.mode = mode; h.arc_len = arc_len;
+    double **arr[12] = {&h.sigma, &h.alpha, &h.beta, &h.omega, &h.eta, &h.zeta, &h.pi_old, &h.pi_new, &h.cp, &h.cx, &h.c1, &h.c2};
+    for (int i = 0; i < 12; ++i) *arr[i] = c->sh_arrays + (size_t)i * nsig;
+    if (arc_len) {
+        h.a_arc = c->sw_buf; h.b_arc = h.a_arc + L; h.w_arc = h.b_arc + L; h.pi_arc = h.w_arc + L;
+        h.stop = (int *)(c->sw_buf + nd); h.skip = h.stop + nsig; h.unsolved_arc = h.skip + nsig;
+    }
+    BICG_HIP(hipMemcpy(c->sh_dev, &h, sizeof h, hipMemcpyHostToDevice));
+    BICG_HIP(hipMemset(c->sh_arrays, 0, sizeof(double) * 12 * (size_t)nsig));
+    if (arc_len) BICG_HIP(hipMemset(c->sw_buf, 0, need));
+    BICG_HIP(hipMemcpy(h.sigma, sigma, sizeof(double) * nsig, hipMemcpyHostToDevice));
+    BICG_HIP(hipMemset(c->p_set, 0, sizeof(double) * (size_t)nsig * st));
+    BICG_HIP(hipMemset(c->x_set, 0, sizeof(double) * (size_t)nsig * st));
+    vec_upload(c, c->x_set, st, x_set_host, nsig);
+    vec_upload(c, c->v.r, st, r_host);
+    BICG_HIP(hipDeviceSynchronize());       // the memsets above ran on the null stream; sc does not wait for it
+
+    if (c->trace_cap < o.max_iter) {
+        c->trace_cap = o.max_iter > 0 ? o.max_iter : 1;
+        c->trace = c->own.regrow(c->trace, 4 * (size_t)c->trace_cap);
+    }
+    Scal hs;
+    memset(&hs, 0, sizeof hs);
+    hs.tol2 = o.tol * o.tol; hs.max_iter = o.max_iter;
+    hs.tr_alpha = c->trace; hs.tr_omega = c->trace + c->trace_cap;
+    hs.tr_beta = c->trace + 2 * (size_t)c->trace_cap; hs.tr_dotr = c->trace + 3 * (size_t)c->trace_cap;
+    hs.sh = c->sh_dev;
+    BICG_HIP(hipMemcpyAsync(c->S, &hs, sizeof hs, hipMemcpyHostToDevice, c->sc));
+    BICG_HIP(hipMemsetAsync(c->counter, 0, sizeof(unsigned) * (kShards + 1) * kCounterStride, c->sc));
+    BICG_HIP(hipMemsetAsync(c->slab + 2 * st, 0, sizeof(double) * 10 * st, c->sc));
+    c->time_kernels = false;
+    sec_begin(c, (o.time_kernels & 2) != 0); c->sec_dump = (o.time_kernels & 4) != 0;
+    return h;
+}
+
 int run_switching(bicg_ctx *c, int mode, double *x_set_host, double *r_host, const double *sigma, int nsig, int seed,
                   const bicg_options *opt_in, bicg_result *res)
 {
@@ -83,55 +142,8 @@ int run_switching(bicg_ctx *c, int mode, double *x_set_host, double *r_host, con
     c->spmv_dir = 0;                     // same first direction for every solve on this context (see run_begin)
     const size_t st = c->stride, n = c->n_loc;
 
-    if (c->sh_cap < nsig) {
-        for (void *p : {(void *)c->sh_dev, (void *)c->sh_arrays, (void *)c->p_set, (void *)c->x_set}) if (p) BICG_HIP(hipFree(p));
-        c->sh_dev = dev_alloc<ShiftDev>(1);
-        c->sh_arrays = dev_alloc<double>(12 * (size_t)nsig);
-        c->p_set = dev_alloc<double>((size_t)nsig * st);
-        c->x_set = dev_alloc<double>((size_t)nsig * st);
-        c->sh_cap = nsig;
-    }
     const int L = o.max_iter + 2;                                    // archive entries 0 .. max_iter + 1
-    const size_t nd = 3 * (size_t)L + (size_t)nsig * L, ni = 2 * (size_t)nsig + (size_t)L;     // (+ the systems still running, per iteration)
-    const size_t need = nd * sizeof(double) + ni * sizeof(int);
-    if (c->sw_cap < need) {
-        if (c->sw_buf) BICG_HIP(hipFree(c->sw_buf));
-        BICG_HIP(hipMalloc((void **)&c->sw_buf, need));
-        c->sw_cap = need;
-    }
-    ShiftDev h;
-    memset(&h, 0, sizeof h);
-    h.nsig = nsig; h.seed = seed; h.mode = mode; h.arc_len = L;
-    double **arr[12] = {&h.sigma, &h.alpha, &h.beta, &h.omega, &h.eta, &h.zeta, &h.pi_old, &h.pi_new, &h.cp, &h.cx, &h.c1, &h.c2};
-    for (int i = 0; i < 12; ++i) *arr[i] = c->sh_arrays + (size_t)i * nsig;
-    h.a_arc = c->sw_buf; h.b_arc = h.a_arc + L; h.w_arc = h.b_arc + L; h.pi_arc = h.w_arc + L;
-    h.stop = (int *)(c->sw_buf + nd); h.skip = h.stop + nsig; h.unsolved_arc = h.skip + nsig;
-    BICG_HIP(hipMemcpy(c->sh_dev, &h, sizeof h, hipMemcpyHostToDevice));
-    BICG_HIP(hipMemset(c->sh_arrays, 0, sizeof(double) * 12 * (size_t)nsig));
-    BICG_HIP(hipMemset(c->sw_buf, 0, need));
-    BICG_HIP(hipMemcpy(h.sigma, sigma, sizeof(double) * nsig, hipMemcpyHostToDevice));
-    BICG_HIP(hipMemset(c->p_set, 0, sizeof(double) * (size_t)nsig * st));
-    BICG_HIP(hipMemset(c->x_set, 0, sizeof(double) * (size_t)nsig * st));
-    vec_upload(c, c->x_set, st, x_set_host, nsig);
-    vec_upload(c, c->v.r, st, r_host);
-    BICG_HIP(hipDeviceSynchronize());
-
-    if (c->trace_cap < o.max_iter) {
-        if (c->trace) BICG_HIP(hipFree(c->trace));
-        c->trace_cap = o.max_iter > 0 ? o.max_iter : 1;
-        c->trace = dev_alloc<double>(4 * (size_t)c->trace_cap);
-    }
-    Scal hs;
-    memset(&hs, 0, sizeof hs);
-    hs.tol2 = o.tol * o.tol; hs.max_iter = o.max_iter;
-    hs.tr_alpha = c->trace; hs.tr_omega = c->trace + c->trace_cap;
-    hs.tr_beta = c->trace + 2 * (size_t)c->trace_cap; hs.tr_dotr = c->trace + 3 * (size_t)c->trace_cap;
-    hs.sh = c->sh_dev;
-    BICG_HIP(hipMemcpyAsync(c->S, &hs, sizeof hs, hipMemcpyHostToDevice, c->sc));
-    BICG_HIP(hipMemsetAsync(c->counter, 0, sizeof(unsigned) * (kShards + 1) * kCounterStride, c->sc));
-    BICG_HIP(hipMemsetAsync(c->slab + 2 * st, 0, sizeof(double) * 10 * st, c->sc));
-    c->time_kernels = false;
-    sec_begin(c, (o.time_kernels & 2) != 0); c->sec_dump = (o.time_kernels & 4) != 0;
+    const ShiftDev h = shifted_setup(c, mode, x_set_host, r_host, sigma, nsig, seed, o, L);
     for (int j = 0; j < nsig; ++j)          // p[sigma] <- b for EVERY shift, src/shifted_switching_solver.c:348
         BICG_HIP(hipMemcpyAsync(c->p_set + (size_t)j * st, c->v.r, sizeof(double) * n, hipMemcpyDeviceToDevice, c->sc));
     {   // streaming policy: matrix + 7 work vectors + the two sets
@@ -292,44 +304,7 @@ int run_shifted(bicg_ctx *c, int mode, double *x_set_host, double *r_host, const
     c->spmv_dir = 0;                     // same first direction for every solve on this context (see run_begin)
     const size_t st = c->stride, n = c->n_loc;
 
-    if (c->sh_cap < nsig) {
-        for (void *p : {(void *)c->sh_dev, (void *)c->sh_arrays, (void *)c->p_set, (void *)c->x_set}) if (p) BICG_HIP(hipFree(p));
-        c->sh_dev = dev_alloc<ShiftDev>(1);
-        c->sh_arrays = dev_alloc<double>(12 * (size_t)nsig);
-        c->p_set = dev_alloc<double>((size_t)nsig * st);
-        c->x_set = dev_alloc<double>((size_t)nsig * st);
-        c->sh_cap = nsig;
-    }
-    ShiftDev h;
-    memset(&h, 0, sizeof h);
-    h.nsig = nsig; h.seed = seed; h.mode = mode;
-    double **arr[12] = {&h.sigma, &h.alpha, &h.beta, &h.omega, &h.eta, &h.zeta, &h.pi_old, &h.pi_new, &h.cp, &h.cx, &h.c1, &h.c2};
-    for (int i = 0; i < 12; ++i) *arr[i] = c->sh_arrays + (size_t)i * nsig;
-    BICG_HIP(hipMemcpy(c->sh_dev, &h, sizeof h, hipMemcpyHostToDevice));
-    BICG_HIP(hipMemset(c->sh_arrays, 0, sizeof(double) * 12 * (size_t)nsig));
-    BICG_HIP(hipMemcpy(h.sigma, sigma, sizeof(double) * nsig, hipMemcpyHostToDevice));
-    BICG_HIP(hipMemset(c->p_set, 0, sizeof(double) * (size_t)nsig * st));        // calloc, src/shifted_solver.c:223
-    BICG_HIP(hipMemset(c->x_set, 0, sizeof(double) * (size_t)nsig * st));
-    vec_upload(c, c->x_set, st, x_set_host, nsig);
-    vec_upload(c, c->v.r, st, r_host);
-    BICG_HIP(hipDeviceSynchronize());       // the memsets above ran on the null stream; sc does not wait for it
-
-    if (c->trace_cap < o.max_iter) {
-        if (c->trace) BICG_HIP(hipFree(c->trace));
-        c->trace_cap = o.max_iter > 0 ? o.max_iter : 1;
-        c->trace = dev_alloc<double>(4 * (size_t)c->trace_cap);
-    }
-    Scal hs;
-    memset(&hs, 0, sizeof hs);
-    hs.tol2 = o.tol * o.tol; hs.max_iter = o.max_iter;
-    hs.tr_alpha = c->trace; hs.tr_omega = c->trace + c->trace_cap;
-    hs.tr_beta = c->trace + 2 * (size_t)c->trace_cap; hs.tr_dotr = c->trace + 3 * (size_t)c->trace_cap;
-    hs.sh = c->sh_dev;
-    BICG_HIP(hipMemcpyAsync(c->S, &hs, sizeof hs, hipMemcpyHostToDevice, c->sc));
-    BICG_HIP(hipMemsetAsync(c->counter, 0, sizeof(unsigned) * (kShards + 1) * kCounterStride, c->sc));
-    BICG_HIP(hipMemsetAsync(c->slab + 2 * st, 0, sizeof(double) * 10 * st, c->sc));
-    c->time_kernels = false;
-    sec_begin(c, (o.time_kernels & 2) != 0); c->sec_dump = (o.time_kernels & 4) != 0;
+    shifted_setup(c, mode, x_set_host, r_host, sigma, nsig, seed, o, 0);
     if (mode == SH_XI)                      // p[sigma] <- b for every shift, src/shifted_solver.c:72
         for (int j = 0; j < nsig; ++j)
             BICG_HIP(hipMemcpyAsync(c->p_set + (size_t)j * st, c->v.r, sizeof(double) * n, hipMemcpyDeviceToDevice, c->sc));

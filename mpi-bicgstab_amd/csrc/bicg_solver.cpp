@@ -219,7 +219,19 @@ void group_defer(bicg_ctx *c, int n, int phase)
 bool stencil_product(const bicg_ctx *c)
 {
     // (whatever order the groups are listed in; across ranks: the halo-free rows are whole planes, StencilDev::z_lo / z_hi)
-    return c->st.on && c->nblk == 0 && c->glist_all && (c->single() ? c->ng_bnd == 0 : c->st_multi);
+    return c->sell.st.on && c->nblk == 0 && c->glist_all && (c->single() ? c->ng_bnd == 0 : c->st_multi);
+}
+
+// Peer-to-peer exchanges are numbered; a landing ring holds kHaloRing of them. When nothing has throttled the senders for a while
+// (no all-reduce or barrier since kHaloRing - 2 exchanges) a barrier goes first. Returns the sequence number of the next exchange.
+static unsigned p2p_next_exchange(bicg_ctx *c, Scal *S)
+{
+    if (c->halo_unsynced >= kHaloRing - 2) {
+        launch_p2p_barrier(c->p2p->red_desc(c->p2p->bar_seq++), c->p2p->timeout_ticks, S, c->sc);
+        c->halo_unsynced = 0;
+    }
+    c->halo_unsynced++;
+    return ++c->halo_seq;
 }
 
 // ---------------------------------------------------------------- distributed SpMV
@@ -235,17 +247,11 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
     SpmvArgs a;
     a.fin = fin;
     a.epi = c->v;
-    a.sell = {c->s_val, c->s_col, c->s_base, c->s_len, c->s_col16, c->s_base16, c->sell_jag ? 1 : 0, c->win_ptr, c->win_runs, c->win_slots, c->sell_perm};
-    a.sell.ubase = c->s_ubase; a.sell.uoff = c->s_uoff; a.sell.vbase = c->s_vbase; a.sell.uval = c->s_uval; a.sell.mbase = c->s_mbase; a.sell.rmask = c->s_rmask;
-    a.sell.sdesc = c->s_desc; a.sell.all_lists = c->sell_all_lists ? 1 : 0; a.sell.uoff8 = c->s_uoff8; a.sell.ystride = c->sell_ystride;
-    a.sell.st = c->st;
-    a.sell.lane_info = c->jagw_fast ? c->lane_info : nullptr; a.sell.win_max_runs = c->win_max_runs;
-    a.sell.win_list = c->win_list; a.sell.win_lptr = c->win_lptr; a.sell.win_ltotal = c->win_ltotal;
+    a.sell = c->sell; a.diag = c->diag; a.offd = c->offd;
+    if (!c->jagw_fast) a.sell.lane_info = nullptr;      // BICG_PLAN="jagw=0": k_spmv_sell's loop instead of the three-trip product
     a.glist = nullptr;
     a.nrows = c->n_loc;
-    a.diag = {c->d_val, c->d_col, c->d_ptr};
     a.diag_col16 = c->d_col16; a.rowsplit = c->rowsplit ? 1 : 0;
-    a.offd = {c->o_val, c->o_col, c->o_ptr};
     a.desc = nullptr; a.nlist = 0;
     a.x = xin; a.y = yout; a.u = u; a.S = S ? S : c->S;
     Scal *const Sh = a.S;        // every kernel of this call reads the same scalar block
@@ -274,7 +280,7 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
     // launch with the exchange inside)
     const bool stencil = stencil_product(c) && (epi == 0 || epi == 3) && !a.has_shift;
     if (epi == 3 && !(stencil && c->single())) die("internal", "CA-BiCGStab's fused q / y epilogue without the plane-marching product");
-    const unsigned g_si = stencil ? stencil_grid(c->st) : sell_grid(c->ng_int, a.groups_per_wg), g_ci = spmv_grid(c->n_int);
+    const unsigned g_si = stencil ? stencil_grid(c->sell.st) : sell_grid(c->ng_int, a.groups_per_wg), g_ci = spmv_grid(c->n_int);
     const unsigned g_sb = sell_grid(c->ng_bnd, a.groups_per_wg), g_cb = spmv_grid(c->n_bnd);
     const bool fused = c->p2p && c->ll_fused && !stencil;
     const bool merged = !c->single() && !stencil && (fused || (!c->p2p && !(c->comm->stream_ordered() && c->overlap) && c->glist_all));
@@ -339,12 +345,7 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
         // peer-to-peer: the send list is stored straight into the landing rings of the ranks that
         // need it, the interior rows run while the values cross the links, one kernel decodes the
         // ring slot into the halo tail of x, then the rows that touch the halo run
-        if (c->halo_unsynced >= kHaloRing - 2) {   // nothing has throttled the senders for a while
-            launch_p2p_barrier(c->p2p->red_desc(c->p2p->bar_seq++), c->p2p->timeout_ticks, Sh, c->sc);
-            c->halo_unsynced = 0;
-        }
-        const unsigned seq = ++c->halo_seq;
-        c->halo_unsynced++;
+        const unsigned seq = p2p_next_exchange(c, Sh);
         const bool lose = c->fault_after > 0 && seq >= (unsigned)c->fault_after;   // BICG_TEST="p2p-fault-after=n" (tests)
         if (fused) {
             // ONE launch: leading workgroups push, the others multiply; halo-touching groups come last
@@ -446,12 +447,7 @@ void halo_only(bicg_ctx *c, double *xin)
 {
     if (c->single() || (c->halo == 0 && c->nsend == 0)) return;
     if (c->p2p) {
-        if (c->halo_unsynced >= kHaloRing - 2) {
-            launch_p2p_barrier(c->p2p->red_desc(c->p2p->bar_seq++), c->p2p->timeout_ticks, c->S, c->sc);
-            c->halo_unsynced = 0;
-        }
-        const unsigned seq = ++c->halo_seq;
-        c->halo_unsynced++;
+        const unsigned seq = p2p_next_exchange(c, c->S);
         launch_halo_push(xin, c->send_idx, c->nsend, c->push_dst0, c->push_stride, seq, c->S, c->sc);
         launch_halo_unpack(c->halo_ring, c->halo, seq, xin + c->n_loc, c->S, c->p2p->timeout_ticks, c->sc);
         return;
@@ -508,14 +504,13 @@ void spmm_pass(bicg_ctx *c, int nvec, const double *sigma_host, bool with_b, boo
     if (!c->single() && !c->p2p && nvec > 1 && !plan_off("halo-set")) halo_set(c, in, nvec);
     else for (int j = 0; j < nvec; ++j) halo_only(c, in + (size_t)j * st);
     // the windowed form (k_spmm_win) reads the shift-major vectors directly and writes Y shift-major into mm_yt
-    const unsigned wslots = c->win_slots ? c->win_slots : (c->s_col16 && !c->sell_jag && c->fw.ncl > 0 ? c->fw.slots : 0u);
+    const unsigned wslots = c->sell.win_slots ? c->sell.win_slots : (c->sell.col16 && !c->sell.jag && c->fw.ncl > 0 ? c->fw.slots : 0u);
     c->mm_win = c->mm_win_env != 0 && spmm_win_vectors(wslots) > 0;
     if (!c->mm_win) launch_rows_from_vectors(in, st, nvec, c->n_loc + c->halo, c->mm_xt, c->sc);
     SpmmArgs a{};
-    a.sell = {c->s_val, c->s_col, c->s_base, c->s_len, c->s_col16, c->s_base16, c->sell_jag ? 1 : 0, c->win_ptr, c->win_runs, c->win_slots, c->sell_perm};
-    a.sell.win_list = c->win_list; a.sell.win_lptr = c->win_lptr; a.sell.win_ltotal = c->win_ltotal;
-    a.sell.lane_info = c->lane_info; a.sell.win_max_runs = c->win_max_runs;
-    a.dptr = c->d_ptr; a.offd = {c->o_val, c->o_col, c->o_ptr};
+    a.sell = c->sell;
+    a.sell.vbase = nullptr;      // sell_layout(): the SpMM kernels have no instantiation of the constant-slice layouts (they read val / col)
+    a.dptr = c->diag.ptr; a.offd = c->offd;
     a.nrows = c->n_loc; a.ngroups = c->ng_int + c->ng_bnd;
     a.xt = c->mm_xt; a.yt = with_b ? nullptr : c->mm_yt; a.b = with_b ? c->v.b : nullptr; a.partial = c->mm_part;
     a.xcd_map = c->mm_xcd ? 1 : 0;
@@ -528,11 +523,11 @@ void spmm_pass(bicg_ctx *c, int nvec, const double *sigma_host, bool with_b, boo
         a.xs = in; a.ys = with_b ? nullptr : out; a.vstride = st; a.nvec = nvec; a.wslots = wslots;
         a.tail_most = c->jag_tail16_max;
         if (const char *sv = test_tok("spmm-skip")) a.dbg = atoi(sv);
-        if (!c->win_slots) a.cl = c->fw;
+        if (!c->sell.win_slots) a.cl = c->fw;
         // the pipelined form where the block qualifies (BICG_PLAN="spmm-window=1": k_spmm_win everywhere)
         c->mm_dma = c->mm_win_env == 3 && !a.dbg && launch_spmm_pipe(a, !c->single(), c->sc, e0, e1) == hipSuccess;
         // ... and its form for ragged rows (jagged slices with x windows: bicg_spmm_jag.hip)
-        if (!c->mm_dma && c->mm_win_env == 3 && c->win_slots && c->win_near16) c->mm_dma = launch_spmm_jpipe(a, !c->single(), c->sc, e0, e1) == hipSuccess;
+        if (!c->mm_dma && c->mm_win_env == 3 && c->sell.win_slots && c->win_near16) c->mm_dma = launch_spmm_jpipe(a, !c->single(), c->sc, e0, e1) == hipSuccess;
         if (!c->mm_dma && launch_spmm_win(a, !c->single(), c->sc, e0, e1) != hipSuccess) die("bicg_spmm", "the windowed kernel could not be launched (BICG_PLAN=spmm-window=0 selects the row-major form)");
     } else {
         if (e0) BICG_HIP(hipEventRecord(e0, c->sc));
@@ -546,30 +541,30 @@ void spmm_pass(bicg_ctx *c, int nvec, const double *sigma_host, bool with_b, boo
 bool spmm_possible(const bicg_ctx *c)
 {
     // (x windows: the kernel keeps a group's runs in 64 LDS entries -- or reads the group's column list, round 6)
-    return c->glist_all && c->nblk == 0 && c->sell_entries > 0 && (c->win_max_runs <= 64 || c->win_list) && (uint64_t)c->stride < (1ull << 25);
+    return c->glist_all && c->nblk == 0 && c->sell_entries > 0 && (c->sell.win_max_runs <= 64 || c->sell.win_list) && (uint64_t)c->stride < (1ull << 25);
 }
 
 void spmm_buffers(bicg_ctx *c)
 {
     if (c->mm_in) return;
     const size_t st = c->stride, ngroups = c->ng_int + c->ng_bnd;
-    c->mm_in = dev_alloc<double>((size_t)kSpmmCols * st + 64);      // (+64: k_spmm_pipe copies 16-byte pairs, the last one may reach one column past a vector)
-    c->mm_xt = dev_alloc<double>((size_t)kSpmmCols * st);
-    c->mm_yt = dev_alloc<double>((size_t)kSpmmCols * st);
-    c->mm_part = dev_alloc<double>((ngroups + 8) * kSpmmCols);
-    c->mm_out = dev_alloc<double>(kSpmmCols);
-    c->mm_sigma = dev_alloc<double>(kSpmmCols);
+    c->mm_in = c->own.alloc<double>((size_t)kSpmmCols * st + 64);      // (+64: k_spmm_pipe copies 16-byte pairs, the last one may reach one column past a vector)
+    c->mm_xt = c->own.alloc<double>((size_t)kSpmmCols * st);
+    c->mm_yt = c->own.alloc<double>((size_t)kSpmmCols * st);
+    c->mm_part = c->own.alloc<double>((ngroups + 8) * kSpmmCols);
+    c->mm_out = c->own.alloc<double>(kSpmmCols);
+    c->mm_sigma = c->own.alloc<double>(kSpmmCols);
     if (!c->single() && (c->halo || c->nsend)) {      // the set exchange (halo_set)
         if ((uint64_t)kSpmmCols * std::max(c->halo, c->nsend) > 0x7fffffffull) die("bicg_spmm", "halo too long for a set exchange");
-        c->set_send = dev_alloc<double>((size_t)kSpmmCols * c->nsend);
-        c->set_recv = dev_alloc<double>((size_t)kSpmmCols * c->halo);
+        c->set_send = c->own.alloc<double>((size_t)kSpmmCols * c->nsend);
+        c->set_recv = c->own.alloc<double>((size_t)kSpmmCols * c->halo);
         std::vector<uint2> sm(c->nsend), rm(c->halo);
         for (int p = 0; p < c->nranks; ++p) {
             for (int i = 0; i < c->scnt[(size_t)p]; ++i) sm[(size_t)(c->sdsp[(size_t)p] + i)] = make_uint2((unsigned)c->sdsp[(size_t)p], (unsigned)c->scnt[(size_t)p]);
             for (int i = 0; i < c->rcnt[(size_t)p]; ++i) rm[(size_t)(c->rdsp[(size_t)p] + i)] = make_uint2((unsigned)c->rdsp[(size_t)p], (unsigned)c->rcnt[(size_t)p]);
         }
-        c->set_smap = dev_upload(sm.data(), sm.size());
-        c->set_rmap = dev_upload(rm.data(), rm.size());
+        c->set_smap = c->own.upload(sm.data(), sm.size());
+        c->set_rmap = c->own.upload(rm.data(), rm.size());
     }
     BICG_HIP(hipMemset(c->mm_in, 0, sizeof(double) * kSpmmCols * st));
     BICG_HIP(hipDeviceSynchronize());      // the memset ran on the null stream: c->sc does not wait for it
@@ -615,7 +610,7 @@ void fetch_scal(bicg_ctx *c);
 bool plain_handover(const bicg_ctx *c)
 {
     return c->handover && c->single() && !c->p2p && c->tail_finish && c->tail_tab && c->hand_shard && c->graph_mode != 1 &&
-           c->nblk == 0 && c->glist_all && c->sell_entries > 0 && !c->sell_jag && !c->win_slots && c->s_col16 && !c->s_vbase &&
+           c->nblk == 0 && c->glist_all && c->sell_entries > 0 && !c->sell.jag && !c->sell.win_slots && c->sell.col16 && !c->sell.vbase &&
            c->ng_bnd == 0 && c->n_int == 0 && c->n_bnd == 0 && !stencil_product(c);
 }
 
@@ -883,9 +878,8 @@ void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in)
 
     // trace storage: the (r,r) history is always kept (progress lines), 4 arrays of max_iter
     if (c->trace_cap < o.max_iter) {
-        if (c->trace) BICG_HIP(hipFree(c->trace));
         c->trace_cap = o.max_iter > 0 ? o.max_iter : 1;
-        c->trace = dev_alloc<double>(4 * (size_t)c->trace_cap);
+        c->trace = c->own.regrow(c->trace, 4 * (size_t)c->trace_cap);
     }
     Scal h;
     memset(&h, 0, sizeof h);
@@ -1000,7 +994,7 @@ bool persist_chunk(bicg_ctx *c, int niter)
         c->halo_unsynced = 0;
     }
     if (a.multi) {
-        if (!c->waitlog) { c->waitlog = dev_alloc<unsigned>(3 * (size_t)kWaitCap); BICG_HIP(hipMemsetAsync(c->waitlog, 0, sizeof(unsigned) * 3 * kWaitCap, c->sc)); }
+        if (!c->waitlog) { c->waitlog = c->own.alloc<unsigned>(3 * (size_t)kWaitCap); BICG_HIP(hipMemsetAsync(c->waitlog, 0, sizeof(unsigned) * 3 * kWaitCap, c->sc)); }
         a.waitlog = c->waitlog; a.waitcap = kWaitCap;
     }
     static const bool want_trace = knob_x("BICG_PERSIST_TRACE") != nullptr;
@@ -1017,20 +1011,20 @@ bool persist_chunk(bicg_ctx *c, int niter)
     if (err != hipSuccess) {
         // nothing ran: hand the chunk back to the multi-launch kernels (every rank sees the same failure: same kernel, same
         // plan limits; the sequence numbers reserved above are simply skipped on all of them)
-        if (dbg) (void)hipFree(dbg);
+        dev_free(dbg, false);
         if (c->nranks > 1) die("persistent kernel", "launch failed on a multi-rank run (BICG_PERSIST=0 selects the multi-launch iteration)");
         fprintf(stderr, "bicgstab_hip: falling back to the multi-launch iteration\n");
         c->persist_on = false;
         return false;
     }
-    if (want_trace && c->method != BICG_PIPE_BICGSTAB) { BICG_HIP(hipStreamSynchronize(c->sc)); BICG_HIP(hipFree(dbg)); }
+    if (want_trace && c->method != BICG_PIPE_BICGSTAB) { BICG_HIP(hipStreamSynchronize(c->sc)); dev_free(dbg); }
     if (want_trace && c->method == BICG_PIPE_BICGSTAB) {
         // 10 ns ticks of one row workgroup (0 start, 1 z and partials published, 2 window staged, 3 product done, 4 omega here,
         // 5 w and partials published, 6 window, 7 product, 8 scalars here) and of the helper (10 / 11: group 1 / 2 published)
         std::vector<unsigned long long> h(64 * 16);
         BICG_HIP(hipStreamSynchronize(c->sc));
         BICG_HIP(hipMemcpy(h.data(), dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        BICG_HIP(hipFree(dbg));
+        dev_free(dbg);
         for (int it = std::max(0, std::min(niter, 32) - 5); it < std::min(niter, 32); ++it)
             for (int who = 0; who < 2; ++who) {
                 const unsigned long long *q = h.data() + (size_t)(it * 2 + who) * 16, *q0 = h.data() + (size_t)(it * 2) * 16;
@@ -1199,7 +1193,7 @@ void probe_pipe_form(bicg_ctx *c, int method, const bicg_options *opt_in)
         t[form] = (now_sec() - t0) / 6.0 * 1.0e3;
         broke = broke || c->hS->breakdown_k != 0 || c->hS->comm_error != 0;
     }
-    BICG_HIP(hipFree(bsyn));
+    dev_free(bsyn);
     if (c->nranks > 1) {      // the slower rank's time counts, and every rank must take the same decision
         const int P = c->nranks;
         std::vector<int> cnt(P, 2 * (int)sizeof(double)), off(P);
@@ -1214,7 +1208,7 @@ void probe_pipe_form(bicg_ctx *c, int method, const bicg_options *opt_in)
     c->fuse_pipe = broke ? rule_form : t[1] <= t[0];
     BICG_HIP(hipMemcpy(c->v.x, keep, sizeof(double) * n, hipMemcpyDeviceToDevice));
     BICG_HIP(hipMemcpy(c->v.r, keep + n, sizeof(double) * n, hipMemcpyDeviceToDevice));
-    BICG_HIP(hipFree(keep));
+    dev_free(keep);
     if (c->rank == 0 && knob_x("BICG_PIPE_PROBE_VERBOSE"))
         fprintf(stderr, "bicgstab_hip: pipelined form probe: separate kernels %.4f ms, SpMV epilogues %.4f ms per iteration -> %s\n", t[0], t[1],
                 c->fuse_pipe ? "epilogues" : "separate kernels");

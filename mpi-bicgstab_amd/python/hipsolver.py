@@ -63,7 +63,7 @@ EXPORTS = [
     "bicg_run_begin", "bicg_run_iterate", "bicg_run_iterate_timed", "bicg_run_end", "bicg_sync", "bicg_trace", "bicg_spmv", "bicg_dot", "bicg_spmv_bench", "bicg_plan_info", "bicg_ctx_flags", "bicg_spmm", "bicg_device_matrix_bytes", "bicg_uniform_entries", "bicg_constant_entries", "bicg_masked_rows", "bicg_stencil_info", "bicg_stencil_rows_per_lane", "bicg_comm_wait_stats", "bicg_plan_collisions", "bicg_product_kernels", "bicg_spmv_matrix_bytes", "bicg_last_shifted_persistent", "bicg_last_spmm_windowed", "bicg_dropin_context", "bicg_dropin_release", "bicg_dropin_stats",
     "bicg_mtx_load_block", "bicg_mtx_free", "bicg_partition", "bicg_halo_plan", "bicg_halo_send_counts", "bicg_halo_send_lists", "bicg_row_blocks", "bicg_window_plan", "bicg_window_slot", "bicg_version", "bicg_has_experiments", "bicg_switch_value", "bicg_switch_unknown", "bicg_stream_bench", "bicg_create_device_csr", "bicg_stencil7_device", "bicg_device_free", "bicg_persist_plan", "bicg_set_plan_threads", "bicg_sell_plan_digest",
     "bicg_reorder_plan", "bicg_permute_block", "bicg_reorder_info",
-    "bicg_solve_multi", "bicg_multi_trace", "bicg_comm_counts",
+    "bicg_solve_multi", "bicg_multi_trace", "bicg_comm_counts", "bicg_device_allocations",
 ]
 
 _lib = None
@@ -120,6 +120,7 @@ def lib():
         for fn in (L.bicg_uniform_entries, L.bicg_constant_entries, L.bicg_masked_rows, L.bicg_spmv_matrix_bytes):
             fn.argtypes = [C.c_void_p]; fn.restype = C.c_ulonglong
         L.bicg_plan_collisions.argtypes = [C.c_void_p]; L.bicg_plan_collisions.restype = C.c_uint
+        L.bicg_device_allocations.argtypes = []; L.bicg_device_allocations.restype = C.c_longlong
         L.bicg_product_kernels.argtypes = [C.c_int]; L.bicg_product_kernels.restype = C.c_uint
         L.bicg_last_shifted_persistent.argtypes = [C.c_void_p]
         L.bicg_last_spmm_windowed.argtypes = [C.c_void_p]
@@ -543,6 +544,11 @@ class Context:
         lib().bicg_plan_info(self.h, out)
         return dict(zip(("rows", "nnz_diag", "nnz_offd", "halo", "row_blocks", "boundary_blocks", "sell_rows",
                          "sell_padding"), list(out)))
+
+
+def device_allocations() -> int:
+    """device allocations of the library's host code not yet freed, in this process (bicg_device_allocations)"""
+    return int(lib().bicg_device_allocations())
 
 
 PRODUCT_KERNELS = {"sell_padded": 1, "sell_jagged": 2, "sell_window_loop": 4, "jagw": 8, "stencil": 16, "csr": 32, "rows": 64, "sell_epilogue": 128,

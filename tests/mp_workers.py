@@ -21,6 +21,46 @@ def _init(rank, world, port):
     return dist
 
 
+def run_ranks(fn, world, kind, wall_limit, prepare=None):
+    """Spawn `world` ranks of worker fn(rank, world, port, kind, outdir) and wait for them, wall_limit seconds at the most; ranks
+    still alive then, or after one of them raised, are ended. prepare(outdir) runs before the ranks start. Asserts that no rank
+    left a fail* file and that every rank left ok* -- unless some left skip*: their texts are returned for the caller to skip on."""
+    import glob
+    import socket
+    import tempfile
+    import time
+    import torch.multiprocessing as mp
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    with tempfile.TemporaryDirectory() as td:
+        if prepare:
+            prepare(td)
+        procs = mp.start_processes(fn, args=(world, port, kind, td), nprocs=world, join=False, start_method="spawn")
+        t0, error = time.monotonic(), None
+        try:
+            while not procs.join(timeout=2.0):
+                if time.monotonic() - t0 > wall_limit:
+                    error = f"the ranks were still running after {wall_limit:.0f} s"
+                    break
+        except Exception as e:      # a rank raised: join() has ended the others
+            error = str(e)
+        for p in procs.processes:
+            if p.is_alive():
+                p.terminate()
+        for p in procs.processes:
+            p.join(10)
+            if p.is_alive():
+                p.kill()
+        fails = sorted(glob.glob(os.path.join(td, "fail*")))
+        assert not fails, open(fails[0]).read()
+        assert error is None, error
+        skips = [open(f).read() for f in sorted(glob.glob(os.path.join(td, "skip*")))]
+        assert skips or len(glob.glob(os.path.join(td, "ok*"))) == world
+        return skips
+
+
 def test_matrix(kind):
     from mpi_bicgstab_amd import synth
     if kind == "offsets":
@@ -209,6 +249,44 @@ def gpu_worker(rank, world, port, kind, outdir):
                 assert np.abs(got["x"] - orc["x"][:, lo:lo + nl]).max() <= 1e-8 * max(1.0, np.abs(orc["x"]).max()), which
             assert orc["switches"] >= 1, "test set-up: no seed switch happened"
         ctx.close()
+        dist.barrier()
+        H.lib().bicg_comm_finalize()
+        dist.destroy_process_group()
+        open(os.path.join(outdir, f"ok{rank}"), "w").write("ok")
+    except Exception:
+        open(os.path.join(outdir, f"fail{rank}"), "w").write(traceback.format_exc())
+        raise
+
+
+def memory_worker(rank, world, port, kind, outdir):
+    """GPU box: tests/test_device_memory_gpu.py across ranks. Every call that allocates lazily runs on a context of the host
+    transport with the peer-to-peer data path; after close() the rank's count of live device allocations is what it was before
+    the context was built (the transport's own memory is not counted)."""
+    try:
+        import numpy as np
+        dist = _init(rank, world, port)
+        from mpi_bicgstab_amd import hipsolver as H, synth
+        from mpi_bicgstab_amd import dist_transport as T
+        from test_device_memory_gpu import check_product, exercise
+
+        T.init_host_transport(0)
+        assert kind.endswith("+p2p")
+        assert H.lib().bicg_comm_enable_p2p() == 0, "peer-to-peer transport did not come up"
+        A = test_matrix(kind.replace("+p2p", ""))
+        diag, offd, counts, displs = synth.split_blocks(A, world, rank)
+        lo, nl = int(displs[rank]), int(counts[rank])
+        before = H.device_allocations()
+        ctx = H.Context(H.HostBlocks(diag, offd, A.rows, counts, displs))
+        fl = ctx.flags()
+        assert fl["p2p"] and fl["ll_fused"] and fl["spmm"] and fl["persist"], fl
+        assert H.device_allocations() > before
+        b = exercise(ctx, A.matvec(np.ones(A.rows))[lo:lo + nl])
+        check_product(b, A, np.ones(A.rows), lo, world)
+        x = np.random.default_rng(3).standard_normal(A.rows)
+        check_product(ctx.spmv(x[lo:lo + nl]), A, x, lo, world)
+        assert not ctx.comm_failed()
+        ctx.close()
+        assert H.device_allocations() == before
         dist.barrier()
         H.lib().bicg_comm_finalize()
         dist.destroy_process_group()

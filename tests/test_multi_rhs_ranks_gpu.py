@@ -14,30 +14,18 @@ a measure on which the oracle itself moves by 2e-11. Everything else is compared
 
 Not exercised here: RCCL with more than one rank (it refuses two ranks on one device) and any real link between GPUs."""
 import functools
-import glob
 import os
-import socket
-import tempfile
-import time
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
 
 import mp_multi_workers as W
+import mp_workers
 import oracle_lib as O
 from test_multi_rhs_gpu import solutions
 
 pytestmark = pytest.mark.gpu
 WALL_LIMIT = 240.0      # seconds per case
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
 
 
 @functools.lru_cache(maxsize=None)
@@ -58,32 +46,10 @@ def reference(name, world, nrhs):
 
 
 def _run(case, name, world, nrhs):
-    with tempfile.TemporaryDirectory() as td:
-        np.savez(os.path.join(td, "oracle.npz"), **reference(name, world, nrhs))
-        procs = mp.start_processes(W.multi_worker, args=(world, _free_port(), f"{case}:{name}", td), nprocs=world, join=False,
-                                   start_method="spawn")
-        t0, error = time.monotonic(), None
-        try:
-            while not procs.join(timeout=2.0):
-                if time.monotonic() - t0 > WALL_LIMIT:
-                    error = f"the ranks were still running after {WALL_LIMIT:.0f} s"
-                    break
-        except Exception as e:      # a rank raised: join() has ended the others
-            error = str(e)
-        for p in procs.processes:
-            if p.is_alive():
-                p.terminate()
-        for p in procs.processes:
-            p.join(10)
-            if p.is_alive():
-                p.kill()
-        fails = sorted(glob.glob(os.path.join(td, "fail*")))
-        assert not fails, open(fails[0]).read()
-        assert error is None, error
-        skips = sorted(glob.glob(os.path.join(td, "skip*")))
-        if skips:
-            pytest.skip(open(skips[0]).read())
-        assert len(glob.glob(os.path.join(td, "ok*"))) == world
+    skips = mp_workers.run_ranks(W.multi_worker, world, f"{case}:{name}", WALL_LIMIT,
+                                 prepare=lambda td: np.savez(os.path.join(td, "oracle.npz"), **reference(name, world, nrhs)))
+    if skips:
+        pytest.skip(skips[0])
 
 
 @pytest.mark.parametrize("name,world,nrhs", [("offsets", 2, 21), ("offsets", 3, 21), ("stencil", 2, 16), ("stencil", 3, 16), ("ragged", 2, 5)])
