@@ -221,20 +221,46 @@ int bicg_stencil7_device(unsigned int m, const double *weights, double **val_d, 
                          unsigned long long *nnz);
 void bicg_device_free(void *p);
 
+/* New values for the matrix of a context, same sparsity pattern: the values are written into the arrays that are already on the
+ * device, at the positions the context's plan defines. Nothing is planned again; every device address of the context, its
+ * iteration graphs, the probed pipelined choice, SpMM and multi-RHS buffers, traces, bicg_ctx_flags, bicg_plan_info,
+ * bicg_device_matrix_bytes and the entry counts below stay what they were, and bicg_device_allocations() is the same after the
+ * call as before it (the host variant's staging buffer is a temporary of the call; the device variant allocates nothing).
+ *   diag_val[nnz_d], offd_val[nnz_o]  in the CSR order of the blocks handed to bicg_create -- the caller's numbering, also on a
+ *                        BICG_FLAG_REORDERED context. offd_val may be NULL when the context has no offd entries; a rank without
+ *                        rows passes empty arrays and the call does nothing. Contexts of bicg_create_device_csr are served too.
+ *   the pattern          neither call takes one: that ptr / col are those of bicg_create is the CALLER'S CONTRACT, nothing checks it.
+ * Local: no transport call, bicg_comm_counts does not move; across ranks every rank updates its own blocks before the next
+ * collective call. The work is ordered on the context's compute stream behind everything already enqueued, and the call is
+ * synchronised on return. The device variant reads its source arrays on that stream: they must be complete before the call (a
+ * caller who fills them on a stream of its own synchronises that stream first).
+ * Values held in shared lists are verified, never rewritten: constant and masked slices (bicg_constant_entries > 0) keep their
+ * values in lists shared between slices, and whether a slice is constant is a property of its values. Before anything is written
+ * every such slice is compared with the new values bit for bit; any difference refuses the call. A caller who WILL change such
+ * values (e.g. the coefficients of a constant-coefficient stencil) creates the context under BICG_PLAN="constant=0", which also
+ * disables masked slices. Unchanged ones -- identity rows of Dirichlet nodes in an otherwise varying matrix -- pass.
+ * Returns 0: done; 1: refused (a list-held value would change), nothing written; -1: NULL context, or a NULL array where entries exist. */
+int bicg_update_values(bicg_ctx *ctx, const double *diag_val, const double *offd_val);               /* host arrays   */
+int bicg_update_values_device(bicg_ctx *ctx, const double *diag_val_d, const double *offd_val_d);    /* device arrays */
+
 /* Matrix residency of the drop-in entry points (section 1 and the shifted ones): the context of the last drop-in call
  * stays resident and is reused when the caller passes the same blocks again -- same arrays, sizes, partition,
  * communicator AND contents (a 64-bit hash over every value / column / row pointer: the matrix may have been edited in
  * place, e.g. by the reference's csr_shift_diagonal, src/matrix.c:518-531). The reference's drivers call a solver 10-28 x
  * on one matrix (src/main_repeat.c:109-132): only the first call pays for plan + upload. All ranks agree on hit / miss.
- * BICG_DROPIN_CACHE=0 in the environment restores create / destroy per call.
+ * BICG_DROPIN_CACHE=0 in the environment restores create / destroy per call. BICG_DROPIN_CACHE=2 (opt-in): when every rank finds
+ * the pattern unchanged and only values edited, the resident context takes them through bicg_update_values instead of being
+ * re-created (still counted as a miss; a rank whose list-held values changed makes every rank re-create).
  *   bicg_dropin_context  the resident context for these blocks (created or reused; collective); owned by the library --
  *                        do NOT bicg_destroy it. Lets a host form b = A*1 with bicg_spmv and then call bicgstab() with
  *                        one upload (host/bicg_main.c)
  *   bicg_dropin_release  drop the resident context now (also happens in bicg_comm_finalize)
- *   bicg_dropin_stats    hits / misses so far */
+ *   bicg_dropin_stats    hits / misses so far
+ *   bicg_dropin_refreshes  misses that were served by bicg_update_values (BICG_DROPIN_CACHE=2) */
 bicg_ctx *bicg_dropin_context(const CSR_Matrix *diag, const CSR_Matrix *offd, const INFO_Matrix *info);
 void bicg_dropin_release(void);
 void bicg_dropin_stats(unsigned int *hits, unsigned int *misses);
+unsigned int bicg_dropin_refreshes(void);
 
 /* Whole solve with host vectors, semantics of section 1 (x_loc/r_loc in-out). */
 int bicg_solve(bicg_ctx *ctx, int method, double *x_loc, double *r_loc, const bicg_options *opt,
@@ -497,6 +523,10 @@ int bicg_set_plan_threads(int n);
 int bicg_persist_plan(const CSR_Matrix *diag, const CSR_Matrix *offd_renumbered, unsigned int gmax, unsigned int summary[8],
                       unsigned int *pbase, unsigned short *pslot, double *pval, unsigned short *rlen, unsigned short *rdiag,
                       unsigned int *win_ptr, unsigned int *win_runs);
+/* ... and where every entry of its pval came from (same arguments and qualification): psrc[e] = index into (diag values followed
+ * by offd values) of pval[e], 0xFFFFFFFF for padding; as many entries as pval (summary[5]). bicg_update_values refills the
+ * persistent plan through this map. Returns 0 when the block qualifies. */
+int bicg_persist_plan_sources(const CSR_Matrix *diag, const CSR_Matrix *offd_renumbered, unsigned int gmax, unsigned int *psrc);
 /* The sliced-ELL plan of a diag block (host only, what bicg_create plans before it uploads anything), read
  * with the switches of the environment, as numbers a test can pin. diag: this rank's diag block; offd_renumbered: its offd block
  * (only the row pointers are read: which rows touch the halo), NULL for one rank; rows_global / nnz_diag_global: rows and diag

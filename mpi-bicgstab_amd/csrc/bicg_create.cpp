@@ -309,6 +309,19 @@ bool persist_build(bicg_ctx *c, const CSR_Matrix *diag, const std::vector<uint32
     if (persist_lds_bytes(a) > lds_max) { a = PersistArgs{}; return false; }
     DevOwner &own = c->persist_own;
     a.pval = own.upload(pval.data(), pval.size());
+    // where every entry of pval came from (bicg_update_values): positions in the block the plan was made from; a reordered
+    // context's are turned into positions in the caller's block, entry for entry in stored order
+    if (c->reordered) {
+        const uint32_t nnz_d = diag->ptr[nrows];
+        std::vector<uint32_t> old_of(nnz_d ? nnz_d : 1);
+        parallel_ranges(nrows, 4096, [&](size_t ra, size_t rb, int) {
+            for (size_t r = ra; r < rb; ++r)
+                for (uint32_t j = diag->ptr[r], k = 0; j < diag->ptr[r + 1]; ++j, ++k) old_of[j] = c->ro_src_ptr_host[c->ro_perm_host[r]] + k;
+        });
+        for (uint32_t &s : P.psrc) if (s != kPersistNoSource && s < nnz_d) s = old_of[s];
+    }
+    c->persist_psrc = own.upload(P.psrc.data(), P.psrc.size());
+    c->persist_entries = pbase[nslices];
     a.pslot = own.upload(pslot.data(), pslot.size());
     a.pbase = own.upload(pbase.data(), pbase.size());
     a.rlen = own.upload(rlen.data(), rlen.size());
@@ -394,6 +407,8 @@ static void ctx_state(bicg_ctx *c, Comm *comm, uint32_t ngroups)
     BICG_HIP(hipMemset(c->shard_ll, 0, sizeof(llword) * 2 * kShardLL * kRedSlots * 2));
     c->alarm = c->own.alloc<int>(1);
     BICG_HIP(hipMemset(c->alarm, 0, sizeof(int)));
+    c->refresh_flag = c->own.alloc<int>(1);
+    BICG_HIP(hipMemset(c->refresh_flag, 0, sizeof(int)));
     BICG_HIP(hipHostMalloc((void **)&c->h_alarm, sizeof(int), hipHostMallocDefault));
     *c->h_alarm = 0;
     if (comm->ranks_on_device > 1) {
@@ -503,6 +518,7 @@ static void ctx_finish(bicg_ctx *c, Comm *comm, uint32_t ngroups, const CSR_Matr
         c->persist_on = all_ranks(comm, mine);
         if (const char *pp = knob_x("BICG_PERSIST_PLAIN")) c->persist_plain = atoi(pp) != 0;
         if (!c->persist_on && mine) { c->persist_own.clear(); c->persist = PersistArgs{}; }
+        if (!c->persist_on) { c->persist_psrc = nullptr; c->persist_entries = 0; }
     }
     trace.mark("transport, persistent plan");
     ctx_streams(c, c->nranks);
@@ -618,6 +634,9 @@ static const CSR_Matrix *reorder_block(bicg_ctx *c, const CSR_Matrix *diag, cons
     memcpy(c->ro_stats, stats, sizeof stats);
     c->ro_perm = c->own.upload(perm.data(), perm.size());
     c->ro_inv = c->own.upload(inv.data(), inv.size());
+    c->ro_src_ptr = c->own.upload(diag->ptr, (size_t)n + 1);
+    c->ro_src_ptr_host.assign(diag->ptr, diag->ptr + n + 1);
+    c->ro_perm_host = std::move(perm);
     return &ro;
 }
 
@@ -839,6 +858,7 @@ bicg_ctx *bicg_create(const CSR_Matrix *diag, const CSR_Matrix *offd, const INFO
     p2p_transport(c, comm, plan, halo);
     ctx_finish(c, comm, plan.ngroups, diag, &halo, trace);
     std::vector<uint32_t>().swap(c->ro_ptr); std::vector<uint32_t>().swap(c->ro_col); std::vector<double>().swap(c->ro_val);
+    std::vector<uint32_t>().swap(c->ro_perm_host); std::vector<uint32_t>().swap(c->ro_src_ptr_host);
     return c;
 }
 

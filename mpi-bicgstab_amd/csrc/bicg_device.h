@@ -606,6 +606,23 @@ void preload_persist_kernels();
 // in: dst[j][new] = src[j][perm[new]]; out: dst[j][old] = src[j][inv[old]] -- gathers with coalesced stores either way
 void launch_permute_in(const double *src, size_t src_stride, double *dst, size_t dst_stride, const uint32_t *perm, uint32_t n, int nvec, hipStream_t st);
 void launch_permute_out(const double *src, size_t src_stride, double *dst, size_t dst_stride, const uint32_t *inv, uint32_t n, int nvec, hipStream_t st);
+// bicg_refresh.hip
+// new values for the resident matrix (bicg_update_values). RefreshSrc: the caller's values in the CSR order of the block handed to
+// bicg_create; the context's row r starts at val[ptr[rowmap ? rowmap[r] : r]] (rowmap: perm of a reordered context, ptr then the
+// caller's row pointers) and is as long as the context's own row pointers (dptr) say.
+struct RefreshSrc {
+    const double   *val;
+    const uint32_t *ptr;
+    const uint32_t *rowmap;
+};
+// *flag = 1 when a constant or masked slice would get a value that differs from its list entry (read-only; no such slices: no launch)
+void launch_refresh_verify(const RefreshSrc &src, const uint32_t *dptr, uint32_t nrows, const SellDev &d, int *flag, hipStream_t st);
+// the slices of the nlist groups in glist (null: groups 0 .. nlist - 1) rewritten in sval, padded or jagged as d says
+void launch_refresh_sell(const RefreshSrc &src, const uint32_t *dptr, uint32_t nrows, const SellDev &d, const uint32_t *glist, uint32_t nlist,
+                         double *sval, hipStream_t st);
+void launch_refresh_rows(const RefreshSrc &src, const uint32_t *dptr, uint32_t nrows, double *dst, hipStream_t st);      // dst[dptr[r] + k] = row r's entry k
+// pval[e] = psrc[e] == 0xFFFFFFFF ? 0.0 : (dval | oval)[psrc[e]]
+void launch_refresh_persist(const double *dval, const double *oval, uint32_t nnz_d, const uint32_t *psrc, uint32_t n, double *pval, hipStream_t st);
 // bicg_exchange.hip
 void launch_apply(Scal *S, int phase, hipStream_t st);
 void launch_halo_pack(const double *x, const uint32_t *send_idx, uint32_t nsend, double *sendbuf, Scal *S, hipStream_t st);

@@ -40,15 +40,16 @@ struct DropinKey {
     int nranks, rank, first_row;
     const Comm *comm;
     const void *p2p;
-    uint64_t hash;
-    bool operator==(const DropinKey &o) const
+    uint64_t hash, vhash;        // pattern (row pointers, columns, partition) / values
+    bool same_pattern(const DropinKey &o) const
     {
         return dv == o.dv && dc == o.dc && dp == o.dp && ov == o.ov && oc == o.oc && op == o.op && rows == o.rows &&
                nnz_d == o.nnz_d && nnz_o == o.nnz_o && n_glob == o.n_glob && nranks == o.nranks && rank == o.rank &&
                first_row == o.first_row && comm == o.comm && p2p == o.p2p && hash == o.hash;
     }
+    bool operator==(const DropinKey &o) const { return same_pattern(o) && vhash == o.vhash; }
 };
-struct DropinCache { bicg_ctx *ctx = nullptr; DropinKey key{}; unsigned hits = 0, misses = 0; } g_dropin;
+struct DropinCache { bicg_ctx *ctx = nullptr; DropinKey key{}; unsigned hits = 0, misses = 0, refreshes = 0; } g_dropin;
 
 uint64_t hash_words(uint64_t h, const void *data, size_t bytes)
 {
@@ -78,24 +79,36 @@ DropinKey dropin_key(const CSR_Matrix *d, const CSR_Matrix *o, const INFO_Matrix
     uint64_t h = 0x243F6A8885A308D3ull;
     h = hash_words(h, d->ptr, sizeof(unsigned) * ((size_t)d->rows + 1));
     h = hash_words(h, d->col, sizeof(unsigned) * (size_t)k.nnz_d);
-    h = hash_words(h, d->val, sizeof(double) * (size_t)k.nnz_d);
+    uint64_t v = hash_words(0x13198A2E03707344ull, d->val, sizeof(double) * (size_t)k.nnz_d);
     if (comm->nranks > 1) {
         h = hash_words(h, o->ptr, sizeof(unsigned) * ((size_t)o->rows + 1));
         h = hash_words(h, o->col, sizeof(unsigned) * (size_t)k.nnz_o);
-        h = hash_words(h, o->val, sizeof(double) * (size_t)k.nnz_o);
+        v = hash_words(v, o->val, sizeof(double) * (size_t)k.nnz_o);
         h = hash_words(h, info->recvcounts, sizeof(int) * (size_t)comm->nranks);
         h = hash_words(h, info->displs, sizeof(int) * (size_t)comm->nranks);
     }
-    k.hash = h;
+    k.hash = h; k.vhash = v;
     return k;
 }
 
-// every rank contributes one flag; true when it is set on all of them
-
-bool dropin_cache_enabled()
+// 0: create / destroy per call; 1 (default): reuse on a full match; 2: ... and update the values in place where only they changed
+int dropin_cache_mode()
 {
-    static const bool enabled = !(getenv("BICG_DROPIN_CACHE") && atoi(getenv("BICG_DROPIN_CACHE")) == 0);
-    return enabled;
+    static const int mode = getenv("BICG_DROPIN_CACHE") ? atoi(getenv("BICG_DROPIN_CACHE")) : 1;
+    return mode;
+}
+bool dropin_cache_enabled() { return dropin_cache_mode() != 0; }
+
+// every rank contributes one level; the lowest of them (the collective all_ranks uses for one flag, bicg_create.cpp)
+int lowest_of_ranks(Comm *comm, int mine)
+{
+    const int P = comm->nranks;
+    if (P == 1) return mine;
+    std::vector<int> cnt(P, (int)sizeof(int)), dsp(P), out(P, mine), in(P, 0);
+    for (int p = 0; p < P; ++p) dsp[p] = p * (int)sizeof(int);
+    comm->alltoallv_host(out.data(), cnt.data(), dsp.data(), in.data(), cnt.data(), dsp.data());
+    in[comm->rank] = mine;
+    return *std::min_element(in.begin(), in.end());
 }
 
 // the resident context for these blocks: reused when nothing changed, rebuilt otherwise (collective)
@@ -113,8 +126,20 @@ bicg_ctx *dropin_context(const CSR_Matrix *diag, const CSR_Matrix *offd, const I
         return g_dropin.ctx;
     }
     const DropinKey key = dropin_key(diag, offd, info, comm);
-    const bool hit = all_ranks(comm, g_dropin.ctx != nullptr && g_dropin.key == key);
-    if (hit) { g_dropin.hits++; return g_dropin.ctx; }
+    // 2: nothing changed; 1: the pattern is the one the context was planned for, values may differ; 0: anything else
+    const int mine = g_dropin.ctx == nullptr ? 0 : g_dropin.key == key ? 2 : (dropin_cache_mode() == 2 && g_dropin.key.same_pattern(key)) ? 1 : 0;
+    const int level = lowest_of_ranks(comm, mine);
+    if (level == 2) { g_dropin.hits++; return g_dropin.ctx; }
+    if (level == 1) {
+        // BICG_DROPIN_CACHE=2: only values were edited, on every rank -- the resident context takes them in place (a rank whose
+        // values are unchanged writes the same bytes again). A rank that must refuse (list-held values changed) makes all re-create.
+        const bool done = bicg_update_values(g_dropin.ctx, diag->val, offd->val) == 0;
+        if (all_ranks(comm, done)) {
+            g_dropin.misses++; g_dropin.refreshes++;
+            g_dropin.key = key;
+            return g_dropin.ctx;
+        }
+    }
     if (g_dropin.ctx) { bicg_destroy(g_dropin.ctx); g_dropin.ctx = nullptr; }
     g_dropin.misses++;
     g_dropin.ctx = bicg_create(diag, offd, info);
@@ -195,6 +220,7 @@ void bicg_dropin_stats(unsigned int *hits, unsigned int *misses)
     if (hits) *hits = g_dropin.hits;
     if (misses) *misses = g_dropin.misses;
 }
+unsigned int bicg_dropin_refreshes(void) { return g_dropin.refreshes; }
 
 
 // BICG_DISPLAY_ERROR=1: what the reference prints when it is compiled with -DDISPLAY_ERROR (src/shifted_switching_solver.c:327-335,

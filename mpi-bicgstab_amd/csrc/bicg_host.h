@@ -6,6 +6,7 @@
 //   bicg_create.cpp   bicg_create / bicg_create_device_csr: halo plan, upload of the diag block's plan (made by bicg_sell_plan.cpp,
 //                     host only: bicg_plan.h) into bicg_ctx::sell / diag / offd, slice descriptors, stencil plan, transport,
 //                     persistent set-up, destroy (clears the context's DevOwner: the one owner of its device memory)
+//   bicg_refresh.cpp  bicg_update_values / bicg_update_values_device: new values for the resident matrix, written in place
 //   bicg_dropin.cpp   the reference's own symbols (solver.h, shifted_solver.h, shifted_switching_solver.h), matrix residency
 //   bicg_api.cpp      the additive handle API (load / fetch / spmv / dot / spmm / info calls)
 #pragma once
@@ -213,6 +214,11 @@ struct bicg_ctx {
     bool f1_done = false;        // phase 1 of the NEXT iteration has already run in the previous launch's epilogue
     // persistent pipelined iteration (bicg_persist.hip, struct PersistArgs): plan + LL buffers; persist.nwg == 0: not available
     PersistArgs persist{};
+    // bicg_update_values refills persist.pval through this map (PersistPlan::psrc, in the CALLER's entry numbering also on a
+    // reordered context); persist_own like the plan itself, and like the caller's row pointers below not matrix storage
+    int *refresh_flag = nullptr;           // bicg_update_values: raised by the read-only pass over list-held values (one word, zero between calls)
+    uint32_t *persist_psrc = nullptr;
+    uint32_t persist_entries = 0;
     bool persist_on = false;     // use it for pipe_bicgstab (every rank agrees); BICG_PERSIST=0 (or off) keeps the multi-launch iteration
     bool persist_plain = true;   // ... and for plain BiCGStab (BICG_PERSIST_PLAIN=0: the five-launch iteration)
     bool last_shifted_persist = false;   // the last shifted solve ran as persistent launches (bicg_result.flags of bicg_solve_shifted)
@@ -293,6 +299,8 @@ struct bicg_ctx {
     int reorder_mode = 0;                // the token's value (ctx_read_switches)
     bool reordered = false;
     uint32_t *ro_perm = nullptr, *ro_inv = nullptr;      // perm[new] = old, inv[old] = new
+    uint32_t *ro_src_ptr = nullptr;      // the caller's row pointers (bicg_update_values takes values in the caller's numbering)
+    std::vector<uint32_t> ro_perm_host, ro_src_ptr_host;     // ... and both on the host while bicg_create builds the persistent plan
     double *ro_stage = nullptr;          // staging for host copies: ro_stage_vecs vectors, `stride` apart; grows with the largest call
     int ro_stage_vecs = 0;
     unsigned long long ro_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // bicg_reorder_info

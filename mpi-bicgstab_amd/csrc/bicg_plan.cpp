@@ -217,6 +217,8 @@ bool persist_plan_host(const CSR_Matrix *diag, const unsigned *optr, const unsig
     for (uint32_t r = 0; r < nrows; ++r) mptr[r + 1] = mptr[r] + (diag->ptr[r + 1] - diag->ptr[r]) + (multi ? optr[r + 1] - optr[r] : 0u);
     std::vector<uint32_t> mcol(mptr[nrows] ? mptr[nrows] : 1);
     std::vector<double> mval(mptr[nrows] ? mptr[nrows] : 1);
+    std::vector<uint32_t> msrc(mptr[nrows] ? mptr[nrows] : 1);      // (PersistPlan::psrc: offd entries count on behind the diag block's)
+    const uint32_t nnz_d = diag->ptr[nrows];
     P.rlen.assign(nrows, 0); P.rdiag.assign(nrows, 0);
     std::vector<char> too_long((size_t)bicg::plan_threads(), 0);
     bicg::parallel_ranges(nrows, 4096, [&](size_t ra, size_t rb, int part) {       // (rows on several threads: each writes its own rows)
@@ -224,8 +226,8 @@ bool persist_plan_host(const CSR_Matrix *diag, const unsigned *optr, const unsig
             uint32_t at = mptr[r];
             const uint32_t dl = diag->ptr[r + 1] - diag->ptr[r], ol = multi ? optr[r + 1] - optr[r] : 0u;
             if (dl + ol > 65535u) { too_long[(size_t)part] = 1; return; }
-            for (uint32_t j = diag->ptr[r]; j < diag->ptr[r + 1]; ++j, ++at) { mcol[at] = diag->col[j]; mval[at] = diag->val[j]; }
-            if (multi) for (uint32_t j = optr[r]; j < optr[r + 1]; ++j, ++at) { mcol[at] = ocol[j]; mval[at] = oval[j]; }
+            for (uint32_t j = diag->ptr[r]; j < diag->ptr[r + 1]; ++j, ++at) { mcol[at] = diag->col[j]; mval[at] = diag->val[j]; msrc[at] = j; }
+            if (multi) for (uint32_t j = optr[r]; j < optr[r + 1]; ++j, ++at) { mcol[at] = ocol[j]; mval[at] = oval[j]; msrc[at] = nnz_d + j; }
             P.rlen[r] = (unsigned short)(dl + ol); P.rdiag[r] = (unsigned short)dl;
         }
     });
@@ -271,6 +273,7 @@ bool persist_plan_host(const CSR_Matrix *diag, const unsigned *optr, const unsig
     const size_t entries = P.pbase[nslices];
     P.pval.assign(entries ? entries : 1, 0.0);
     P.pslot.assign(entries ? entries : 1, 0);
+    P.psrc.assign(entries ? entries : 1, kPersistNoSource);
     for (uint32_t g = 0; g < nwg; ++g) {
         const uint32_t s0 = g * spw, s1 = std::min(nslices, s0 + spw);
         P.max_entries = std::max(P.max_entries, P.pbase[s1] - P.pbase[s0]);
@@ -283,6 +286,7 @@ bool persist_plan_host(const CSR_Matrix *diag, const unsigned *optr, const unsig
                 for (uint32_t j = mptr[r], k = 0; j < mptr[r + 1]; ++j, ++k) {
                     const size_t e = (size_t)P.pbase[sl] + (size_t)k * kSlice + lane;
                     P.pval[e] = mval[j];
+                    P.psrc[e] = msrc[j];
                     P.pslot[e] = (unsigned short)slot_of(g, mcol[j]);
                 }
             }
@@ -313,6 +317,19 @@ extern "C" int bicg_persist_plan(const CSR_Matrix *diag, const CSR_Matrix *offd_
     if (rdiag) std::copy(P.rdiag.begin(), P.rdiag.end(), rdiag);
     if (win_ptr) std::copy(P.wptr.begin(), P.wptr.end(), win_ptr);
     if (win_runs) std::copy(P.runs.begin(), P.runs.end(), win_runs);
+    return 0;
+}
+
+// ... and the source map of its pval entries (PersistPlan::psrc, what bicg_update_values refills pval through): psrc holds as many
+// entries as pval (summary[5] of bicg_persist_plan). Returns 0 when the block qualifies.
+extern "C" int bicg_persist_plan_sources(const CSR_Matrix *diag, const CSR_Matrix *offd_renumbered, unsigned int gmax, unsigned int *psrc)
+{
+    bicg::PersistPlan P;
+    const bool multi = offd_renumbered != nullptr;
+    if (!bicg::persist_plan_host(diag, multi ? offd_renumbered->ptr : nullptr, multi ? offd_renumbered->col : nullptr,
+                                 multi ? offd_renumbered->val : nullptr, gmax, P))
+        return 1;
+    if (psrc) std::copy(P.psrc.begin(), P.psrc.begin() + P.pbase[P.nslices], psrc);
     return 0;
 }
 

@@ -26,8 +26,10 @@ struct PersistPlan {
     std::vector<uint32_t> runs;                   // pairs {first column, (first slot << 16) | length}
     std::vector<uint32_t> pbase;                  // [nslices + 1]
     std::vector<double> pval;                     // padded slices
+    std::vector<uint32_t> psrc;                   // [pval entries] where the entry came from: index into (diag values | offd values), kPersistNoSource: padding
     std::vector<unsigned short> pslot;
 };
+constexpr uint32_t kPersistNoSource = 0xFFFFFFFFu;
 bool persist_plan_host(const CSR_Matrix *diag, const unsigned *optr, const unsigned *ocol, const double *oval, unsigned gmax,
                        PersistPlan &P);
 

@@ -64,6 +64,7 @@ EXPORTS = [
     "bicg_mtx_load_block", "bicg_mtx_free", "bicg_partition", "bicg_halo_plan", "bicg_halo_send_counts", "bicg_halo_send_lists", "bicg_row_blocks", "bicg_window_plan", "bicg_window_slot", "bicg_version", "bicg_has_experiments", "bicg_switch_value", "bicg_switch_unknown", "bicg_stream_bench", "bicg_create_device_csr", "bicg_stencil7_device", "bicg_device_free", "bicg_persist_plan", "bicg_set_plan_threads", "bicg_sell_plan_digest",
     "bicg_reorder_plan", "bicg_permute_block", "bicg_reorder_info",
     "bicg_solve_multi", "bicg_multi_trace", "bicg_comm_counts", "bicg_device_allocations",
+    "bicg_update_values", "bicg_update_values_device", "bicg_persist_plan_sources", "bicg_dropin_refreshes",
 ]
 
 _lib = None
@@ -152,6 +153,10 @@ def lib():
         L.bicg_reorder_plan.argtypes = [C.POINTER(CSRMatrix), C.c_int, _up, C.POINTER(C.c_ulonglong)]
         L.bicg_permute_block.argtypes = [C.POINTER(CSRMatrix), _up, _up, _up, _dp]
         L.bicg_reorder_info.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+        L.bicg_update_values.argtypes = [C.c_void_p, _dp, _dp]
+        L.bicg_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bicg_dropin_refreshes.argtypes = []; L.bicg_dropin_refreshes.restype = C.c_uint
+        L.bicg_persist_plan_sources.argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.c_uint, _up]
         for name in ("bicgstab", "ca_bicgstab", "pipe_bicgstab"):
             getattr(L, name).argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp]
         L.pipe_bicgstab_rr.argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp,
@@ -307,6 +312,28 @@ class Context:
         if not self.h:
             raise RuntimeError("bicg_create_device_csr refused the matrix")
         return self, int(nnz.value), float(secs.value), t_gen
+
+    def update_values(self, diag_val, offd_val=None) -> int:
+        """New values for the resident matrix, same sparsity pattern (bicg_update_values): arrays in the CSR order of the blocks
+        the context was created from -- numpy arrays (host variant) or CUDA torch tensors (device variant) --, or a CSR /
+        HostBlocks whose values are taken. Returns 0 done, 1 refused (a value held in a list shared between constant or masked
+        slices would change; nothing was written), -1 an array is missing."""
+        if isinstance(diag_val, HostBlocks):
+            diag_val, offd_val = diag_val._keep[0], diag_val._keep[3]
+        elif isinstance(diag_val, CSR):
+            diag_val = diag_val.val
+        if isinstance(offd_val, CSR):
+            offd_val = offd_val.val
+        if hasattr(diag_val, "data_ptr"):            # torch tensors on the device
+            keep = [None if t is None else t.contiguous() for t in (diag_val, offd_val)]
+            for t in keep:
+                if t is not None and (not t.is_cuda or str(t.dtype) != "torch.float64"):
+                    raise TypeError("update_values: device arrays are CUDA float64 tensors")
+            ptrs = [C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None for t in keep]
+            return int(lib().bicg_update_values_device(self.h, ptrs[0], ptrs[1]))
+        d = None if diag_val is None else np.ascontiguousarray(diag_val, dtype=np.float64)
+        o = None if offd_val is None else np.ascontiguousarray(offd_val, dtype=np.float64)
+        return int(lib().bicg_update_values(self.h, None if d is None or d.size == 0 else _d(d), None if o is None or o.size == 0 else _d(o)))
 
     def close(self):
         if self.h:
@@ -606,6 +633,28 @@ def persist_plan(blocks: HostBlocks, nranks: int, gmax: int):
     assert rc2 == 0
     return dict(spw=spw, rpt=rpt, nwg=nwg, win_slots=win_slots, max_runs=max_runs, max_entries=max_entries, entries=entries, halo=halo,
                 pbase=pbase, pslot=pslot[:entries], pval=pval[:entries], rlen=rlen, rdiag=rdiag, wptr=wptr, runs=runs[:2 * nruns].reshape(-1, 2))
+
+
+def persist_plan_sources(blocks: HostBlocks, nranks: int, gmax: int, entries: int):
+    """Source map of the persistent plan's pval (bicg_persist_plan_sources): `entries` indices into (diag values, then offd values),
+    0xFFFFFFFF for padding; None when the block does not qualify. entries: persist_plan(...)["entries"]."""
+    offd_p, keep = None, None
+    if nranks > 1:
+        halo, _, _, ren = halo_plan(blocks, nranks)
+        nz = int(blocks.offd.ptr[blocks.offd.rows])
+        ren = np.ascontiguousarray(ren[:max(nz, 1)], dtype=np.uint32)
+        keep = (ren,)
+        o = CSRMatrix(blocks.offd.val, ren.ctypes.data_as(_up), blocks.offd.ptr, nz, blocks.offd.rows, blocks.n_loc + halo)
+        offd_p = C.byref(o)
+    psrc = np.zeros(max(entries, 1), dtype=np.uint32)
+    rc = lib().bicg_persist_plan_sources(C.byref(blocks.diag), offd_p, gmax, psrc.ctypes.data_as(_up))
+    del keep
+    return None if rc != 0 else psrc[:entries]
+
+
+def dropin_refreshes() -> int:
+    """drop-in calls that updated the resident context's values in place (BICG_DROPIN_CACHE=2; bicg_dropin_refreshes)"""
+    return int(lib().bicg_dropin_refreshes())
 
 
 # bicg_sell_plan_digest (include/bicgstab_hip.h section 5): names of the summary's entries and of the arrays behind the digests
