@@ -413,7 +413,11 @@ enum { BICG_FLAG_P2P = 1, BICG_FLAG_LL_FUSED = 2, BICG_FLAG_OVERLAP = 4, BICG_FL
        BICG_FLAG_HANDOVER = 32768  /* plain BiCGStab on this context closes its dot groups by hand-over: the producing kernel leaves
                                      shard totals, the kernel that consumes the scalars adds them and applies the recurrence
                                      (one rank, padded 16-bit layout; BICG_PLAN="handover=0" selects the producer-side finish).
-                                     Same sums, same order: bit-identical */ };
+                                     Same sums, same order: bit-identical */,
+       BICG_FLAG_TAIL_FINISH = 65536 /* ticket-mode dot groups whose workgroups come from ONE launch close by the tail finish (the
+                                     launch's last workgroups add the partial sums); clear under BICG_TAIL_FINISH=0, hipGraph replay
+                                     and the peer-to-peer transport: every group then closes by arrival tickets, as a group that
+                                     spans several launches always may. Same sums, same order: bit-identical */ };
 unsigned int bicg_ctx_flags(bicg_ctx *ctx);
 /* The reordering of a context with BICG_FLAG_REORDERED: the stats of bicg_reorder_plan (section 5) with out[7] = microseconds
  * bicg_create spent on ordering + permuting. Returns 0; 1 and zeros when the context is not reordered. */

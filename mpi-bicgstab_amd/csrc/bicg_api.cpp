@@ -350,6 +350,7 @@ unsigned int bicg_ctx_flags(bicg_ctx *c)
     if (c->constant_entries) f |= BICG_FLAG_CONSTANT;
     if (c->reordered) f |= BICG_FLAG_REORDERED;
     if (plain_handover(c)) f |= BICG_FLAG_HANDOVER;
+    if (c->tail_finish && !c->p2p && c->tail_tab && c->graph_mode != 1) f |= BICG_FLAG_TAIL_FINISH;
     return f;
 }
 

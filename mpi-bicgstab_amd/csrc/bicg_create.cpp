@@ -393,7 +393,7 @@ static void ctx_state(bicg_ctx *c, Comm *comm, uint32_t ngroups)
     BICG_HIP(hipMemset(c->tail_tab, 0, sizeof(llword) * (size_t)c->nslots * kTailStride));
     c->tail_shard = c->own.alloc<llword>((size_t)kShards * kRedSlots * 2);
     BICG_HIP(hipMemset(c->tail_shard, 0, sizeof(llword) * kShards * kRedSlots * 2));
-    if (const char *sv = knob_x("BICG_TAIL_FINISH")) c->tail_finish = atoi(sv) != 0;
+    if (const char *sv = getenv("BICG_TAIL_FINISH")) c->tail_finish = atoi(sv) != 0;      // 0: every ticket-mode group closes by arrival tickets
     c->hand_shard = c->own.alloc<llword>((size_t)2 * kRedSlots * kShards * 2);
     BICG_HIP(hipMemset(c->hand_shard, 0, sizeof(llword) * 2 * kRedSlots * kShards * 2));
     c->Sbuf = c->own.alloc<Scal>(2);

@@ -287,6 +287,18 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
     const unsigned g_sall = sell_grid(c->ng_int + c->ng_bnd, a.groups_per_wg);
     red.expected = merged ? g_sall + g_ci + g_cb : g_si + g_ci + g_sb + g_cb;
     red.slot_base = 0;
+    if (red.tail_seq) {
+        // The tail finish keeps the group's last min(expected, kShards) workgroups IN LAUNCH ORDER behind to add the slots. All of
+        // them must belong to the launch that comes last on this stream: a stayer of an earlier launch would wait for slots that
+        // only a later launch writes, and that launch cannot start behind it. So a group whose workgroups come from several
+        // launches, the last of them smaller than that, closes by arrival tickets instead -- same slots, same shard membership,
+        // same order of every sum, hence the same bits. (The launch with the exchange inside never carries a tail finish.)
+        const unsigned grids[4] = {merged ? g_sall : g_si, g_ci, merged || c->single() ? 0u : g_sb, c->single() ? 0u : g_cb};
+        unsigned launches = 0, last = 0;
+        for (unsigned g : grids)
+            if (g) { ++launches; last = g; }
+        if (launches > 1 && last < std::min<unsigned>(red.expected, (unsigned)kShards)) red.tail_seq = 0;
+    }
     a.red = red;
     if (red.hand) c->hand.nsh = std::min<unsigned>(red.expected, (unsigned)kShards);      // what the consuming kernel will find
     if (red.wave && (ndot > 0 || epi)) c->grp.nparts = red.expected * (kBlock / 64);   // one partial per wavefront
@@ -825,8 +837,12 @@ void fetch_scal(bicg_ctx *c)
         // BICG_P2P_SOFT_FAIL=1: report through bicg_comm_failed() and stop iterating instead of
         // exiting (bench.py then falls back to the RCCL collectives)
         const char *soft = getenv("BICG_P2P_SOFT_FAIL");
-        // one rank, no peer-to-peer path: the only waits are those between the workgroups of a persistent launch (they spin on each
-        // other and need to be co-resident: another long-running kernel on the same GPU can starve them) or on a dot group's producers
+        // no peer-to-peer path: the only waits are those between the workgroups of a persistent launch (they spin on each other
+        // and need to be co-resident: another long-running kernel on the same GPU can starve them) or, in every other launch, those
+        // of a dot group's finishing workgroups on its producers
+        if (!c->p2p && !c->soft_fail && (!soft || atoi(soft) == 0) && !c->persist_on)
+            die("dot group", "the producers of a dot group never delivered their partial sums: the workgroups that finish the group "
+                             "gave up waiting for them (tail finish; BICG_TAIL_FINISH=0 selects arrival tickets)");
         if (!c->p2p && !c->soft_fail && (!soft || atoi(soft) == 0))
             die("persistent kernel", "workgroups waited for each other longer than the time-out -- is another kernel holding CUs of this GPU? "
                                      "(BICG_PERSIST=0 selects the multi-launch iteration)");

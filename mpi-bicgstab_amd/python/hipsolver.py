@@ -509,7 +509,7 @@ class Context:
         return bool(lib().bicg_comm_failed(self.h))
 
     FLAGS = {"p2p": 1, "ll_fused": 2, "overlap": 4, "col16": 8, "all_sell": 16, "jagged": 32, "spmm": 64, "window": 128, "rowsplit": 256, "persist": 512,
-             "fuse_pipe": 1024, "pipe_probed": 2048, "uniform": 4096, "constant": 8192, "reordered": 16384, "handover": 32768}
+             "fuse_pipe": 1024, "pipe_probed": 2048, "uniform": 4096, "constant": 8192, "reordered": 16384, "handover": 32768, "tail_finish": 65536}
 
     def flags(self):
         f = int(lib().bicg_ctx_flags(self.h))

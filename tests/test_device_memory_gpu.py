@@ -9,19 +9,7 @@ context that frees the right memory must also still point at it. y = A x is comp
 src/matrix.c:498-516; rows of at most 2048 entries, as in tests/test_gpu_parity.py) and with synth.CSR.matvec. numpy adds a row's
 products pairwise, the kernels in stored order: two sums of the same n products differ by at most 2 gamma_n sum |a_ij x_j| with
 gamma_n = n u / (1 - n u), u = 2^-53 (Higham, Accuracy and Stability of Numerical Algorithms, section 4.2); the bar below takes
-n + 2 for n, which covers the denominator and the rounding of the bar itself for the rows used here (n <= 3000).
-
-The context with CSR row blocks (random_rows: 17 sliced-ELL groups and 14 CSR row blocks) runs exercise() without the plain
-solver and the shifted family. Those put a ticket-mode dot group across the two launches of one product -- 17 sliced-ELL workgroups
-on slots 0..16, then 14 k_spmv workgroups on slots 17..30, Reduce::expected = 31 -- and the tail finish (tail_shard_sum,
-csrc/bicg_reduce.h) keeps the last min(expected, kShards = 32) workgroups IN LAUNCH ORDER behind to add the slots: here all 31, so
-sliced-ELL workgroup `order` waits for slot 30 - order, which the CSR launch writes, and that launch cannot start before the
-sliced-ELL launch has ended (one stream). After the 4 s patience the consumers give up (Scal::comm_error, reported by fetch_scal);
-seen on the GPU with this matrix. The condition -- a dot group over two launches whose second launch has fewer than
-min(expected, 32) workgroups -- is in code this file's subject does not touch and needs a change of its own (no tail finish for a
-group that spans launches); no other test meets it: the golden ragged_n400 is planned all-CSR, the other random_rows tests only
-multiply. Until then the case runs the calls whose dots are finished by a later kernel (pipe_bicgstab: consumer-side finish) or by
-kernels of their own (solve_multi): the trace still regrows, the multi-RHS buffers and their trace are allocated."""
+n + 2 for n, which covers the denominator and the rounding of the bar itself for the rows used here (n <= 3000)."""
 import numpy as np
 import pytest
 
@@ -46,17 +34,15 @@ def check_product(y, A, x, lo=0, nranks=1):
     assert np.all(np.abs(y - A.matvec(x)[rows]) <= 2.0 * (lens + 2) * 2.0 ** -53 * mag)
 
 
-def exercise(ctx, b, ticket_dots=True):
-    """every call of a context that allocates lazily (the solvers' results are other tests' business). ticket_dots=False: without
-    the products that carry a ticket-mode dot group (plain BiCGStab, the shifted family) -- the module docstring says for whom"""
+def exercise(ctx, b):
+    """every call of a context that allocates lazily (the solvers' results are other tests' business)"""
     n = len(b)
     rng = np.random.default_rng(7)
-    ctx.solve("bicgstab" if ticket_dots else "pipe_bicgstab", b, tol=0.0, max_iter=3, check_every=3, record_trace=1)
+    ctx.solve("bicgstab", b, tol=0.0, max_iter=3, check_every=3, record_trace=1)
     ctx.solve("pipe_bicgstab", b, tol=0.0, max_iter=7, check_every=7, record_trace=1)      # the trace regrows
-    if ticket_dots:
-        ctx.solve_shifted(b, 0.01 * (np.arange(3) + 1.0), 1, tol=0.0, max_iter=4, check_every=4)
-        ctx.solve_shifted(b, 0.01 * (np.arange(5) + 1.0), 2, tol=0.0, max_iter=4, check_every=4)      # the shift buffers regrow
-        ctx.solve_shifted(b, 0.02 * 2.0 ** np.arange(5), 4, tol=0.0, max_iter=4, check_every=2, which="shifted_lopbicg_switching")
+    ctx.solve_shifted(b, 0.01 * (np.arange(3) + 1.0), 1, tol=0.0, max_iter=4, check_every=4)
+    ctx.solve_shifted(b, 0.01 * (np.arange(5) + 1.0), 2, tol=0.0, max_iter=4, check_every=4)      # the shift buffers regrow
+    ctx.solve_shifted(b, 0.02 * 2.0 ** np.arange(5), 4, tol=0.0, max_iter=4, check_every=2, which="shifted_lopbicg_switching")
     if ctx.flags()["spmm"]:
         ctx.spmm(rng.standard_normal((3, n)), 0.25 * np.arange(3))
     ctx.solve_multi(np.stack([b, 0.5 * b, rng.standard_normal(n)]), tol=0.0, max_iter=4, check_every=2, record_trace=1)
@@ -114,7 +100,7 @@ CASES = {
     # the list-driven window
     "mesh_rcm": lambda t: _host(lambda: _mesh_rcm(t)) + (
         lambda c, fl: fl["jagged"] and fl["window"] and _kernel_of_a_product(c, 117 ** 3) == ["jagw_list"],),
-    # CSR row blocks (see the module docstring: without the calls that carry ticket-mode dot groups)
+    # CSR row blocks beside slices: 17 sliced-ELL groups and 14 row blocks, two launches per product
     "random_rows": lambda t: _host(lambda: synth.random_rows(5_000, 40, seed=11, empty_frac=0.15,
                                                              long_rows={5: 2500, 1777: 2999, 2999: 2100})) + (
         lambda c, fl: not fl["all_sell"] and c.plan_info()["sell_rows"] < 5_000 and "csr" in _kernel_of_a_product(c, 5_000),),
@@ -133,7 +119,7 @@ def test_a_context_gives_back_every_allocation(name, tmp_path_factory):
     ctx = build()
     assert H.device_allocations() > before
     assert reached(ctx, ctx.flags()), (name, ctx.flags(), ctx.plan_info())
-    b = exercise(ctx, A.matvec(np.ones(A.rows)), ticket_dots=name != "random_rows")
+    b = exercise(ctx, A.matvec(np.ones(A.rows)))
     check_product(b, A, np.ones(A.rows))
     check_product(ctx.spmv(x), A, x)
     ctx.close()

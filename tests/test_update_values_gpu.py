@@ -73,12 +73,6 @@ def csr_blocks(ctx):
 
 def solves(ctx, A2):
     b = A2.matvec(np.ones(A2.rows))
-    if 0 < csr_blocks(ctx) < 32 and ctx.plan_info()["sell_rows"] > 0:
-        # Few CSR row blocks beside slices: a product's ticket-mode dot group spans two launches, and where the second (CSR) launch
-        # has fewer than 32 workgroups the tail finish of plain BiCGStab does not survive it (tail_shard_sum, csrc/bicg_reduce.h;
-        # profiles/NOTES.md and tests/test_device_memory_gpu.py say more; older than this file). Such a context is solved with
-        # pipe_bicgstab here, whose dots a later kernel finishes; the case "row_blocks_48" runs plain BiCGStab on the same stored forms.
-        return [solved(ctx, "pipe_bicgstab", b, tol=0.0, max_iter=7, check_every=7, record_trace=1)]
     out = [solved(ctx, "bicgstab", b)]
     if ctx.flags()["persist"]:
         out.append(solved(ctx, "pipe_bicgstab", b))
@@ -166,8 +160,7 @@ CASES = {
     "reordered": (lambda: _mesh("random"), {"reorder": 1}, lambda c: c.flags()["reordered"] and c.flags()["persist"]),
     "row_blocks_beside_slices": (lambda: synth.random_rows(8000, 12, seed=3, empty_frac=0.1, long_rows=LONG_ROWS), {},
                                  lambda c: 0 < c.plan_info()["sell_rows"] < c.plan_info()["rows"] and not c.flags()["all_sell"] and csr_blocks(c) == 11),
-    # (the matrix above has 11 CSR row blocks, too few for plain BiCGStab on a mixed context -- see solves(); this one has 48, so the
-    # plain solve, to convergence, runs on CSR row blocks beside slices as well)
+    # (11 CSR row blocks above: the product's second launch is smaller than the 32 shards; 48 here)
     "row_blocks_48": (mixed_rows, {}, lambda c: 0 < c.plan_info()["sell_rows"] < c.plan_info()["rows"] and csr_blocks(c) >= 32),
     "rows_over_lanes": (lambda: synth.banded(4099, 200), {}, lambda c: c.flags()["rowsplit"]),
 }
