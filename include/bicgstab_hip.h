@@ -341,6 +341,43 @@ int bicg_solve_multi(bicg_ctx *ctx, int method, double *x_loc_set, double *r_loc
  * iterations, may be NULL. Returns 0; non-zero when nothing was recorded or the column is out of range. */
 int bicg_multi_trace(bicg_ctx *ctx, int column, double *alpha, double *omega, double *beta, double *dot_r);
 
+/* DEVICE-RESIDENT VECTORS: the calls above for a caller whose vectors are in device memory. Every pointer is a device pointer to
+ * fp64 on the context's device, 8-byte aligned, in the CALLER'S numbering also on a BICG_FLAG_REORDERED context; `stream` is the
+ * caller's hipStream_t (NULL: the null stream). Apart from where the vectors live the semantics are those of the host variants,
+ * and what they return is bit-identical to the host variant's on the same context: k, x, r, the result fields and the traces.
+ *   bicg_load_device         fills the context's x and r; bicg_run and bicg_run_begin / _iterate / _end then work unchanged.
+ *                            x0_d == NULL keeps the x the context already holds (warm start: a time stepper starts from the
+ *                            previous solution without moving it) -- defined when the last call that wrote the context's x was
+ *                            a bicg_load* or a bicg_run* / bicg_solve* on it. b_d is always required: a solve overwrites r.
+ *   bicg_fetch_device        either pointer may be NULL, as in bicg_fetch.
+ *   bicg_solve_device        load + solve + fetch; x_d / r_d in-out.
+ *   bicg_spmv_device         the collective product y = A x; y_d must not alias x_d.
+ *   bicg_solve_multi_device  bicg_solve_multi with column j at set + j * ld, ld >= local_rows, columns in-out. Collectivity,
+ *                            return values, freezing, the res entries, the traces and the memory behaviour are bicg_solve_multi's;
+ *                            a refused call touches neither set.
+ * Stream ordering, both ways, without a host synchronisation added by the crossing: before the library touches the caller's arrays
+ * it records an event on `stream` and makes its compute stream wait for it; after the last kernel that reads or writes them it
+ * records an event on the compute stream and makes `stream` wait for it. So what the caller enqueued on `stream` before the call
+ * (the kernel that fills b_d) is complete before the arrays are read, and what it enqueues on `stream` after the call is ordered
+ * behind it: b_d may be overwritten on `stream` right after bicg_load_device, x_d read on `stream` right after bicg_fetch_device,
+ * and a caching allocator that recycles memory in stream order stays safe. Work on OTHER streams is the caller's to order. The
+ * solving calls synchronise with the host where the host variants do, at their convergence checks; bicg_spmv_device ends with the
+ * host variant's check of the peers on a peer-to-peer context and otherwise returns without a host wait; load and fetch never wait.
+ * The calls must NOT be made while `stream` is being captured into a graph.
+ * The crossing is one launch (csrc/bicg_vecio.hip) and allocates nothing -- no staging buffer, also on a reordered context:
+ * bicg_device_allocations() is the same after load / fetch / solve / spmv as before, and bicg_solve_multi_device allocates what
+ * bicg_solve_multi does on a context's first multi call and nothing later. A rank without rows passes NULL (or empty) arrays,
+ * takes part in every collective and copies nothing.
+ * Return: 0 done (the solving calls: their k); -1 NULL context, or a NULL required array where rows exist; -2 as bicg_solve_multi,
+ * and for ld < local_rows. Across ranks a rank whose own arrays bicg_solve_multi_device has to refuse still takes part in the
+ * call's argument check, and the other ranks then return -1 as for any disagreement. */
+int bicg_load_device(bicg_ctx *ctx, const double *x0_d, const double *b_d, void *stream);
+int bicg_fetch_device(bicg_ctx *ctx, double *x_d, double *r_d, void *stream);
+int bicg_solve_device(bicg_ctx *ctx, int method, double *x_d, double *r_d, const bicg_options *opt, bicg_result *res, void *stream);
+int bicg_spmv_device(bicg_ctx *ctx, const double *x_d, double *y_d, void *stream);
+int bicg_solve_multi_device(bicg_ctx *ctx, int method, double *x_set_d, double *r_set_d, size_t ld, int nrhs,
+                            const bicg_options *opt, bicg_result *res /* nrhs entries, may be NULL */, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * 4. Kernel-level entry points (parity tests, benchmarks).
  *   bicg_spmv        <- MPI_csr_spmv_ovlap, reference src/matrix.c:428-441 (collective)

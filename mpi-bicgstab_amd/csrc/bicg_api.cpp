@@ -1,5 +1,6 @@
 // bicg_api.cpp -- the additive handle API of include/bicgstab_hip.h: load / fetch / timed iteration / spmv / dot / spmm /
-// shifted residuals / information calls. Split from bicg_solver.cpp in round 5; see bicg_host.h.
+// shifted residuals / information calls, and the load / fetch / solve / spmv variants for vectors in device memory (bicg_*_device,
+// DESIGN.md section 4.19). Split from bicg_solver.cpp in round 5; see bicg_host.h.
 #include "bicg_host.h"
 
 // ---- a reordered context's host copies (vec_upload / vec_download, bicg_host.h): through the staging buffer and the permutation
@@ -40,7 +41,72 @@ void reorder_download(bicg_ctx *c, double *host, const double *dev, size_t dev_s
     if (!async) BICG_HIP(hipStreamSynchronize(c->sc));
 }
 
+// ---- a caller's device vectors (the *_device entry points; bicg_host.h)
+void cross_begin(bicg_ctx *c, hipStream_t user)
+{
+    if (!c->cross_ev[0]) for (auto &e : c->cross_ev) BICG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    // (the compute stream is non-blocking: not even the null stream orders itself against it)
+    BICG_HIP(hipEventRecord(c->cross_ev[0], user));
+    BICG_HIP(hipStreamWaitEvent(c->sc, c->cross_ev[0], 0));
+}
+void cross_end(bicg_ctx *c, hipStream_t user)
+{
+    BICG_HIP(hipEventRecord(c->cross_ev[1], c->sc));
+    BICG_HIP(hipStreamWaitEvent(user, c->cross_ev[1], 0));
+}
+void cross_in(bicg_ctx *c, double *dev0, const double *user0, double *dev1, const double *user1, size_t dev_stride, size_t ld, int nvec)
+{
+    if (c->phantom) {      // the phantom row's entries are zero in every vector
+        for (double *dev : {dev0, dev1})
+            for (int j = 0; dev && j < nvec; ++j) BICG_HIP(hipMemsetAsync(dev + (size_t)j * dev_stride, 0, sizeof(double), c->sc));
+        return;
+    }
+    VecPair p[2];
+    int np = 0;
+    if (user0) p[np++] = VecPair{user0, ld, dev0, dev_stride};
+    if (user1) p[np++] = VecPair{user1, ld, dev1, dev_stride};
+    launch_vecio(p, np, c->reordered ? c->ro_perm : nullptr, c->n_loc, nvec, c->sc);
+}
+void cross_out(bicg_ctx *c, double *user0, const double *dev0, double *user1, const double *dev1, size_t dev_stride, size_t ld, int nvec)
+{
+    if (c->phantom) return;
+    VecPair p[2];
+    int np = 0;
+    if (user0) p[np++] = VecPair{dev0, dev_stride, user0, ld};
+    if (user1) p[np++] = VecPair{dev1, dev_stride, user1, ld};
+    launch_vecio(p, np, c->reordered ? c->ro_inv : nullptr, c->n_loc, nvec, c->sc);
+}
+
 extern "C" {
+
+int bicg_load_device(bicg_ctx *c, const double *x0_d, const double *b_d, void *stream)
+{
+    if (!c || (!c->phantom && !b_d)) return -1;
+    use_device(c);
+    cross_begin(c, (hipStream_t)stream);
+    cross_in(c, c->v.x, x0_d, c->v.r, b_d, c->stride, c->n_loc, 1);      // x0_d null: the context's x stays (warm start)
+    cross_end(c, (hipStream_t)stream);
+    return 0;
+}
+
+int bicg_fetch_device(bicg_ctx *c, double *x_d, double *r_d, void *stream)
+{
+    if (!c) return -1;
+    use_device(c);
+    cross_begin(c, (hipStream_t)stream);      // what the caller still does with x_d / r_d on its stream comes first
+    cross_out(c, x_d, c->v.x, r_d, c->v.r, c->stride, c->n_loc, 1);
+    cross_end(c, (hipStream_t)stream);
+    return 0;
+}
+
+int bicg_solve_device(bicg_ctx *c, int method, double *x_d, double *r_d, const bicg_options *opt, bicg_result *res, void *stream)
+{
+    if (!c || (!c->phantom && (!x_d || !r_d))) return -1;
+    bicg_load_device(c, x_d, r_d, stream);
+    const int k = run_solver(c, method, opt, res);
+    bicg_fetch_device(c, x_d, r_d, stream);
+    return k;
+}
 
 int bicg_load(bicg_ctx *c, const double *x0, const double *b)
 {
@@ -119,6 +185,21 @@ int bicg_spmv(bicg_ctx *c, const double *x, double *y)
     vec_download(c, y, c->v.s, c->stride, 1, true);
     if (c->p2p) fetch_scal(c);      // also reports a peer that never delivered its halo values
     else BICG_HIP(hipStreamSynchronize(c->sc));
+    return 0;
+}
+
+int bicg_spmv_device(bicg_ctx *c, const double *x_d, double *y_d, void *stream)
+{
+    if (!c || (!c->phantom && (!x_d || !y_d))) return -1;
+    use_device(c);
+    reset_scal(c);
+    cross_begin(c, (hipStream_t)stream);
+    cross_in(c, c->v.p, x_d, nullptr, nullptr, c->stride, c->n_loc, 1);
+    c->time_kernels = false;
+    spmv(c, c->v.p, c->v.s, 0, nullptr, c->red(0, PH_NONE));
+    cross_out(c, y_d, c->v.s, nullptr, nullptr, c->stride, c->n_loc, 1);
+    cross_end(c, (hipStream_t)stream);
+    if (c->p2p) fetch_scal(c);      // as bicg_spmv: reports a peer that never delivered its halo values; otherwise no host wait
     return 0;
 }
 

@@ -1154,6 +1154,7 @@ void bicg_destroy(bicg_ctx *c)
     }
     for (auto &e : c->tev) (void)hipEventDestroy(e);
     for (auto &e : c->region_ev) if (e) (void)hipEventDestroy(e);
+    for (auto &e : c->cross_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->sec_ev) (void)hipEventDestroy(e);
     for (auto &ge : c->graph_exec) if (ge) (void)hipGraphExecDestroy(ge);
     if (c->sc) (void)hipStreamDestroy(c->sc);

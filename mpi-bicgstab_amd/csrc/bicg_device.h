@@ -606,6 +606,12 @@ void preload_persist_kernels();
 // in: dst[j][new] = src[j][perm[new]]; out: dst[j][old] = src[j][inv[old]] -- gathers with coalesced stores either way
 void launch_permute_in(const double *src, size_t src_stride, double *dst, size_t dst_stride, const uint32_t *perm, uint32_t n, int nvec, hipStream_t st);
 void launch_permute_out(const double *src, size_t src_stride, double *dst, size_t dst_stride, const uint32_t *inv, uint32_t n, int nvec, hipStream_t st);
+// bicg_vecio.hip
+// the caller's device vectors crossing into / out of the solver's (the *_device entry points): npairs <= 2 (source, destination)
+// pairs x nvec columns, dst[j][i] = src[j][idx ? idx[i] : i]; 16-byte accesses on every side whose pointer and leading dimension
+// allow them, one launch when both pairs take the same accesses
+struct VecPair { const double *src; size_t src_ld; double *dst; size_t dst_ld; };
+void launch_vecio(const VecPair *pairs, int npairs, const uint32_t *idx, uint32_t n, int nvec, hipStream_t st);
 // bicg_refresh.hip
 // new values for the resident matrix (bicg_update_values). RefreshSrc: the caller's values in the CSR order of the block handed to
 // bicg_create; the context's row r starts at val[ptr[rowmap ? rowmap[r] : r]] (rowmap: perm of a reordered context, ptr then the

@@ -8,7 +8,7 @@
 //                     persistent set-up, destroy (clears the context's DevOwner: the one owner of its device memory)
 //   bicg_refresh.cpp  bicg_update_values / bicg_update_values_device: new values for the resident matrix, written in place
 //   bicg_dropin.cpp   the reference's own symbols (solver.h, shifted_solver.h, shifted_switching_solver.h), matrix residency
-//   bicg_api.cpp      the additive handle API (load / fetch / spmv / dot / spmm / info calls)
+//   bicg_api.cpp      the additive handle API (load / fetch / spmv / dot / spmm / info calls; their *_device variants)
 #pragma once
 
 #include <algorithm>
@@ -254,6 +254,9 @@ struct bicg_ctx {
     hipStream_t sc = nullptr, sm = nullptr;   // compute, communication
     hipEvent_t ev_pack[kEvRing] = {}, ev_halo[kEvRing] = {}, ev_dots[kEvRing] = {}, ev_red[kEvRing] = {};
     unsigned i_pack = 0, i_halo = 0, i_dots = 0, i_red = 0;
+    // the *_device entry points (cross_begin / cross_end below): [0] recorded on the caller's stream, the compute stream waits for
+    // it; [1] recorded on the compute stream, the caller's stream waits for it. Timing disabled; created by the first such call
+    hipEvent_t cross_ev[2] = {nullptr, nullptr};
 
     // deferred dot group (pipelined variant: all-reduce overlaps the next SpMV)
     bool pend = false;
@@ -420,6 +423,17 @@ inline void vec_download(bicg_ctx *c, double *host, const double *dev, size_t de
         else BICG_HIP(hipMemcpy(host + (size_t)j * n, dev + (size_t)j * dev_stride, sizeof(double) * n, hipMemcpyDeviceToHost));
     }
 }
+
+// A caller's DEVICE vectors crossing (the *_device entry points, bicg_api.cpp): nvec columns `ld` doubles
+// apart on the caller's side, dev_stride apart on the solver's, in the caller's numbering also on a reordered context -- one
+// launch of bicg_vecio.hip on the compute stream for up to two vectors (a null caller pointer: that vector stays out), no staging
+// buffer, no allocation. A rank without rows copies nothing: cross_in zeroes its phantom row instead, as host_in's zeros would.
+// cross_begin / cross_end order the compute stream behind the caller's stream and the caller's stream behind the compute stream
+// through the context's two events, without a host wait.
+void cross_begin(bicg_ctx *c, hipStream_t user);
+void cross_end(bicg_ctx *c, hipStream_t user);
+void cross_in(bicg_ctx *c, double *dev0, const double *user0, double *dev1, const double *user1, size_t dev_stride, size_t ld, int nvec);
+void cross_out(bicg_ctx *c, double *user0, const double *dev0, double *user1, const double *dev1, size_t dev_stride, size_t ld, int nvec);
 
 // every transport collective of a context goes through these two: they count (bicg_comm_counts)
 inline void ctx_allreduce(bicg_ctx *c, double *dev, int n, hipStream_t st)

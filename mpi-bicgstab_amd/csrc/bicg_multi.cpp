@@ -15,6 +15,9 @@
 // k_multi_apply, which adds the rows in a fixed order: the scalars, hence the flags the host reads, are the same bytes on every rank,
 // so the ranks cannot disagree about the next collective. On a peer-to-peer context the products use its data path (halo_only /
 // spmv) while these all-reduces go through the transport underneath (c->comm->allreduce_sum): correct, not optimised.
+//
+// bicg_solve_multi_device is the same call on the caller's device arrays: solve_multi_any below serves
+// both, they differ in how a set's columns cross (vec_upload / vec_download against cross_in / cross_out, bicg_host.h).
 #include "bicg_host.h"
 
 namespace {
@@ -79,7 +82,9 @@ void multi_finish(bicg_ctx *c, int phase, int nv, unsigned nwg)
 // Collective: did every rank pass the same arguments? Each rank writes what the sequence of collectives depends on into its row
 // of the gather buffer (every value an integer a double holds exactly; tol as the two halves of its bit pattern), one all-reduce
 // gathers the rows, every rank compares them all -- so every rank reaches the same verdict.
-bool multi_agree(bicg_ctx *c, int method, int nrhs, const bicg_options &o, bool spmm)
+// local_bad: this rank's own arrays are refusable (device variant: a missing array, ld < local_rows) -- the others cannot see that, so it
+// travels with the arguments and every rank refuses together
+bool multi_agree(bicg_ctx *c, int method, int nrhs, const bicg_options &o, bool spmm, bool local_bad = false)
 {
     const int P = c->nranks;
     unsigned long long tb = 0;
@@ -89,23 +94,23 @@ bool multi_agree(bicg_ctx *c, int method, int nrhs, const bicg_options &o, bool 
                             (double)(tb >> 32), spmm ? 1.0 : 0.0};
     std::vector<double> all((size_t)P * kRedRow, 0.0);
     std::copy(mine, mine + 7, all.begin() + (size_t)c->rank * kRedRow);
+    all[(size_t)c->rank * kRedRow + 7] = local_bad ? 1.0 : 0.0;
     BICG_HIP(hipMemcpyAsync(c->mt_red, all.data(), sizeof(double) * all.size(), hipMemcpyHostToDevice, c->sc));
     BICG_HIP(hipStreamSynchronize(c->sc));      // (all is pageable: the copy has left it before the transport may touch the stream)
     ctx_allreduce(c, c->mt_red, P * kRedRow, c->sc);
     BICG_HIP(hipMemcpyAsync(all.data(), c->mt_red, sizeof(double) * all.size(), hipMemcpyDeviceToHost, c->sc));
     BICG_HIP(hipStreamSynchronize(c->sc));
     for (int p = 0; p < P; ++p)
-        if (memcmp(all.data() + (size_t)p * kRedRow, mine, sizeof mine) != 0) return false;
+        if (memcmp(all.data() + (size_t)p * kRedRow, mine, sizeof mine) != 0 || all[(size_t)p * kRedRow + 7] != 0.0) return false;
     return true;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bicg_solve_multi(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_set, int nrhs, const bicg_options *opt_in,
-                     bicg_result *res)
+// bicg_solve_multi (device = false: host arrays, ld = local_rows) and bicg_solve_multi_device (the caller's device arrays, columns
+// ld apart, `user` its stream): the same call but for how a set's columns cross, vec_upload / vec_download or cross_in / cross_out
+int solve_multi_any(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_set, size_t ld, int nrhs, const bicg_options *opt_in,
+                    bicg_result *res, bool device, hipStream_t user)
 {
+    if (!c) return -1;
     bicg_options o;
     if (opt_in) o = *opt_in; else bicg_default_options(&o);
     if (o.max_iter < 0) o.max_iter = 0;
@@ -114,12 +119,14 @@ int bicg_solve_multi(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_s
         // collective from here on: a rank whose own arguments are refusable still takes part in the check, or the others would wait
         use_device(c);
         multi_red_buffer(c);
-        if (!multi_agree(c, method, nrhs, o, c->spmm_ok && !plan_off("spmm"))) return -1;
+        const bool bad = device && !c->phantom && (!x_loc_set || !r_loc_set || ld < c->n_loc);
+        if (!multi_agree(c, method, nrhs, o, c->spmm_ok && !plan_off("spmm"), bad) && !bad) return -1;
     }
-    if (method != BICG_BICGSTAB || nrhs < 1) return -2;
+    if (device && !c->phantom && (!x_loc_set || !r_loc_set)) return -1;
+    if (method != BICG_BICGSTAB || nrhs < 1 || (device && !c->phantom && ld < c->n_loc)) return -2;
     use_device(c);
     std::vector<double> ph_x, ph_r;        // a context without rows holds one phantom row: zeros in, nothing out (host_in)
-    if (c->phantom) { ph_x.assign((size_t)nrhs, 0.0); ph_r.assign((size_t)nrhs, 0.0); x_loc_set = ph_x.data(); r_loc_set = ph_r.data(); }
+    if (c->phantom && !device) { ph_x.assign((size_t)nrhs, 0.0); ph_r.assign((size_t)nrhs, 0.0); x_loc_set = ph_x.data(); r_loc_set = ph_r.data(); }
 
     scal_reset(c);                         // the per-column products read the context's scalar block like bicg_spmv
     c->time_kernels = false;
@@ -148,8 +155,14 @@ int bicg_solve_multi(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_s
         h.trace = tracing ? c->mt_trace : nullptr;
         h.trace_cap = tracing ? c->mt_trace_cap : 0;
         BICG_HIP(hipMemcpyAsync(c->mt_S, &h, sizeof h, hipMemcpyHostToDevice, c->sc));
-        vec_upload(c, v.x, c->stride, x_loc_set + (size_t)j0 * n, nv, true);
-        vec_upload(c, v.r, c->stride, r_loc_set + (size_t)j0 * n, nv, true);
+        if (device) {
+            cross_begin(c, user);
+            cross_in(c, v.x, x_loc_set + (size_t)j0 * ld, v.r, r_loc_set + (size_t)j0 * ld, c->stride, ld, nv);
+            cross_end(c, user);
+        } else {
+            vec_upload(c, v.x, c->stride, x_loc_set + (size_t)j0 * n, nv, true);
+            vec_upload(c, v.r, c->stride, r_loc_set + (size_t)j0 * n, nv, true);
+        }
         BICG_HIP(hipStreamSynchronize(c->sc));      // (h is reused below; the uploads are not part of the timed span)
 
         // ---- set-up phase (src/solver.c:74-83): s = A x ; r = b - s ; r# = r ; p = r ; (r,r)
@@ -186,8 +199,14 @@ int bicg_solve_multi(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_s
         const double t2 = now_sec();
         t_total += t2 - t0; t_iter += t2 - t1;
 
-        vec_download(c, x_loc_set + (size_t)j0 * n, v.x, c->stride, nv, true);
-        vec_download(c, r_loc_set + (size_t)j0 * n, v.r, c->stride, nv, true);
+        if (device) {
+            cross_begin(c, user);
+            cross_out(c, x_loc_set + (size_t)j0 * ld, v.x, r_loc_set + (size_t)j0 * ld, v.r, c->stride, ld, nv);
+            cross_end(c, user);
+        } else {
+            vec_download(c, x_loc_set + (size_t)j0 * n, v.x, c->stride, nv, true);
+            vec_download(c, r_loc_set + (size_t)j0 * n, v.r, c->stride, nv, true);
+        }
         BICG_HIP(hipStreamSynchronize(c->sc));
         for (int j = 0; j < nv; ++j) {
             kmax = std::max(kmax, h.k[j]);
@@ -210,6 +229,22 @@ int bicg_solve_multi(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_s
     if (res)
         for (int j = 0; j < nrhs; ++j) { res[j].seconds = t_total; res[j].iter_seconds = t_iter; }
     return kmax;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bicg_solve_multi(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_set, int nrhs, const bicg_options *opt_in,
+                     bicg_result *res)
+{
+    return solve_multi_any(c, method, x_loc_set, r_loc_set, c ? c->n_loc : 0, nrhs, opt_in, res, false, nullptr);
+}
+
+int bicg_solve_multi_device(bicg_ctx *c, int method, double *x_set_d, double *r_set_d, size_t ld, int nrhs, const bicg_options *opt_in,
+                            bicg_result *res, void *stream)
+{
+    return solve_multi_any(c, method, x_set_d, r_set_d, ld, nrhs, opt_in, res, true, (hipStream_t)stream);
 }
 
 int bicg_multi_trace(bicg_ctx *c, int column, double *alpha, double *omega, double *beta, double *dot_r)

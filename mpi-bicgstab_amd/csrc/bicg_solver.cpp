@@ -1178,6 +1178,9 @@ void probe_pipe_form(bicg_ctx *c, int method, const bicg_options *opt_in)
     c->pipe_probed = true;
     use_device(c);
     const size_t n = c->n_loc;
+    // (the copies below run on the null stream, which the compute stream does not order itself against: after bicg_load_device x and
+    // r may still be on their way in. After bicg_load the stream is idle and this returns at once)
+    BICG_HIP(hipStreamSynchronize(c->sc));
     double *keep = dev_alloc<double>(2 * n);
     BICG_HIP(hipMemcpy(keep, c->v.x, sizeof(double) * n, hipMemcpyDeviceToDevice));
     BICG_HIP(hipMemcpy(keep + n, c->v.r, sizeof(double) * n, hipMemcpyDeviceToDevice));

@@ -65,6 +65,7 @@ EXPORTS = [
     "bicg_reorder_plan", "bicg_permute_block", "bicg_reorder_info",
     "bicg_solve_multi", "bicg_multi_trace", "bicg_comm_counts", "bicg_device_allocations",
     "bicg_update_values", "bicg_update_values_device", "bicg_persist_plan_sources", "bicg_dropin_refreshes",
+    "bicg_load_device", "bicg_fetch_device", "bicg_solve_device", "bicg_spmv_device", "bicg_solve_multi_device",
 ]
 
 _lib = None
@@ -156,6 +157,15 @@ def lib():
         L.bicg_update_values.argtypes = [C.c_void_p, _dp, _dp]
         L.bicg_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.bicg_dropin_refreshes.argtypes = []; L.bicg_dropin_refreshes.restype = C.c_uint
+        # device-resident vectors: device pointers and the caller's hipStream_t as void *
+        L.bicg_load_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bicg_fetch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bicg_solve_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Options), C.POINTER(Result), C.c_void_p]
+        L.bicg_spmv_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bicg_solve_multi_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(Options),
+                                              C.POINTER(Result), C.c_void_p]
+        for fn in (L.bicg_load_device, L.bicg_fetch_device, L.bicg_solve_device, L.bicg_spmv_device, L.bicg_solve_multi_device):
+            fn.restype = C.c_int
         L.bicg_persist_plan_sources.argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.c_uint, _up]
         for name in ("bicgstab", "ca_bicgstab", "pipe_bicgstab"):
             getattr(L, name).argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp]
@@ -205,6 +215,54 @@ def switch_value(var: str, name: str):
 
 def _d(a):
     return a.ctypes.data_as(_dp)
+
+
+# ---- device-resident vectors (bicg_*_device): CUDA float64 torch tensors wherever the vector calls take numpy arrays
+def tensor_form(*arrs) -> bool:
+    """Is this call in its device form -- is one of the arrays (None: not given) a torch tensor? Then all of them are CUDA float64
+    tensors, or TypeError: decided from the arguments alone, before the library or a context is touched."""
+    given = [a for a in arrs if a is not None]
+    if not any(hasattr(a, "data_ptr") for a in given):
+        return False
+    for a in given:
+        if not hasattr(a, "data_ptr") or not a.is_cuda or str(a.dtype) != "torch.float64":
+            raise TypeError("device vectors are CUDA float64 torch tensors (and a call takes tensors or numpy arrays, not both)")
+    return True
+
+
+def _torch_stream(stream):
+    """the torch stream a device call is ordered on: the current one, a torch.cuda.Stream, or a raw hipStream_t as an integer"""
+    import torch
+    if stream is None:
+        return torch.cuda.current_stream()
+    if hasattr(stream, "cuda_stream"):
+        return stream
+    return torch.cuda.ExternalStream(int(stream)) if int(stream) else torch.cuda.default_stream()
+
+
+def _vp(t):
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+def _vec1(t, n, what, inplace=False):
+    """a tensor as n doubles one after the other (a copy when it is not; never when the library writes into it)"""
+    if t.numel() != n:
+        raise ValueError(f"{what}: {t.numel()} entries for {n} rows")
+    if t.dim() == 1 and (n <= 1 or t.stride(0) == 1):
+        return t
+    if inplace:
+        raise ValueError(f"{what}: an in-place vector is one-dimensional with stride 1")
+    return t.contiguous().reshape(-1)
+
+
+def _set2(t, nrhs, n, what, inplace=False):
+    """a tensor as nrhs columns of n doubles, (tensor, ld): a 2-D tensor whose rows are contiguous and at least n apart is passed
+    as it is, with its row stride as ld; anything else is made contiguous first"""
+    if t.dim() == 2 and t.shape == (nrhs, n) and (n <= 1 or t.stride(1) == 1) and (nrhs == 1 or t.stride(0) >= n):
+        return t, (n if nrhs == 1 else int(t.stride(0)))
+    if inplace:
+        raise ValueError(f"{what}: an in-place set is [nrhs][n] with contiguous rows at least n apart")
+    return t.reshape(nrhs, n).contiguous(), n
 
 
 def window_plan(A: CSR, group_rows: int = 256, max_slots: int = 4096, gap: int = 8):
@@ -354,7 +412,13 @@ class Context:
         return o
 
     def solve(self, method: str, b, x0=None, **kw):
-        """Semantics of the reference solver call: returns dict(k, x, r, result)."""
+        """Semantics of the reference solver call: returns dict(k, x, r, result). b / x0 as CUDA float64 torch tensors: the device
+        form (bicg_solve_device) -- x and r come back as fresh tensors on the same device, b and x0 stay as they are; inplace=True
+        makes x0 (required then) and b the in-out arrays themselves. stream: the torch.cuda.Stream (or raw stream) the call is
+        ordered on, default the current one."""
+        if tensor_form(b, x0):
+            return self._solve_device(method, b, x0, kw)
+        kw.pop("stream", None); kw.pop("inplace", None)
         x = np.zeros(self.n) if x0 is None else np.array(x0, dtype=np.float64)
         r = np.array(b, dtype=np.float64)
         kw.setdefault("quiet", 1)
@@ -363,12 +427,60 @@ class Context:
         k = lib().bicg_solve(self.h, METHODS[method], _d(x), _d(r), C.byref(o), C.byref(res))
         return dict(k=k, x=x, r=r, dot_r=res.dot_r, dot_zero=res.dot_zero, result=res)
 
+    def _solve_device(self, method, b, x0, kw):
+        import torch
+        st, inplace = _torch_stream(kw.pop("stream", None)), bool(kw.pop("inplace", False))
+        with torch.cuda.stream(st):
+            if inplace:
+                if x0 is None:
+                    raise ValueError("solve(inplace=True) takes x0: it becomes x")
+                x, r = _vec1(x0, self.n, "x0", True), _vec1(b, self.n, "b", True)
+            else:
+                x = torch.zeros(self.n, dtype=torch.float64, device=b.device) if x0 is None else _vec1(x0, self.n, "x0").clone()
+                r = _vec1(b, self.n, "b").clone()
+        kw.setdefault("quiet", 1)
+        o = self.options(**kw)
+        res = Result()
+        k = lib().bicg_solve_device(self.h, METHODS[method], _vp(x), _vp(r), C.byref(o), C.byref(res), C.c_void_p(st.cuda_stream))
+        return dict(k=k, x=x, r=r, dot_r=res.dot_r, dot_zero=res.dot_zero, result=res)
+
+    def _solve_multi_device(self, B, X0, method, nrhs, kw):
+        import torch
+        st, inplace = _torch_stream(kw.pop("stream", None)), bool(kw.pop("inplace", False))
+        if nrhs is None:
+            nrhs = B.shape[0] if B.dim() == 2 else B.numel() // max(self.n, 1)
+        with torch.cuda.stream(st):
+            if inplace:
+                if X0 is None:
+                    raise ValueError("solve_multi(inplace=True) takes X0: it becomes x")
+                (x, ldx), (r, ldr) = _set2(X0, nrhs, self.n, "X0", True), _set2(B, nrhs, self.n, "B", True)
+                if ldx != ldr:
+                    raise ValueError("solve_multi(inplace=True): X0 and B have the same row stride")
+            else:
+                r, ldr = _set2(B, nrhs, self.n, "B")
+                r = r.clone(memory_format=torch.contiguous_format)
+                x = (torch.zeros((nrhs, self.n), dtype=torch.float64, device=B.device) if X0 is None
+                     else _set2(X0, nrhs, self.n, "X0")[0].clone(memory_format=torch.contiguous_format))
+                ldr = self.n
+        kw.setdefault("quiet", 1)
+        o = self.options(**kw)
+        res = (Result * max(nrhs, 1))()
+        rc = lib().bicg_solve_multi_device(self.h, METHODS[method], _vp(x), _vp(r), ldr, nrhs, C.byref(o), res, C.c_void_p(st.cuda_stream))
+        results = list(res)[:nrhs] if rc >= 0 else []
+        self._multi_k = [q.iterations for q in results]
+        return dict(k=np.array(self._multi_k, dtype=np.int64), x=x, r=r, results=results, rc=rc)
+
     def solve_multi(self, B, X0=None, method: str = "bicgstab", nrhs=None, **kw):
         """Plain BiCGStab on the rows of B [nrhs][n] as independent right-hand sides of the resident matrix, 16 columns per pass
         over the matrix (bicg_solve_multi): dict(k [nrhs] int array, x [nrhs][n], r [nrhs][n], results [nrhs] of Result, rc = the
         call's return value: the largest k, or the negative code of a refused call -- x and r are then X0 and B). Collective
         across ranks (rc = -1: the ranks passed different arguments); nrhs: the number of columns where B cannot tell -- a rank
-        without rows (n = 0) passes it with empty arrays."""
+        without rows (n = 0) passes it with empty arrays. B / X0 as CUDA float64 torch tensors: the device form
+        (bicg_solve_multi_device), x and r fresh [nrhs][n] tensors; inplace=True: X0 (required) and B are the in-out sets themselves,
+        2-D with contiguous rows whose stride (>= n, the same for both) is passed as ld. stream: as for solve."""
+        if tensor_form(B, X0):
+            return self._solve_multi_device(B, X0, method, nrhs, kw)
+        kw.pop("stream", None); kw.pop("inplace", None)
         if nrhs is None:
             r = np.array(B, dtype=np.float64).reshape(-1, self.n)
             nrhs = r.shape[0]
@@ -439,7 +551,18 @@ class Context:
             raise RuntimeError("bicg_spmm: the matrix is not entirely on the sliced-ELL path")
         return y, ms.value
 
-    def load(self, x0, b):
+    def load(self, x0, b, stream=None):
+        """x0 and b into the context's x and r (bicg_load). CUDA float64 torch tensors: bicg_load_device on `stream` (default: the
+        current torch stream), where x0=None keeps the x the context holds -- a warm start from the previous solution."""
+        if tensor_form(x0, b):
+            import torch
+            st = _torch_stream(stream)
+            with torch.cuda.stream(st):      # (a copy made contiguous here is made, and later freed, in the order of that stream)
+                x0 = None if x0 is None else _vec1(x0, self.n, "x0")
+                b = _vec1(b, self.n, "b")
+            if lib().bicg_load_device(self.h, _vp(x0), _vp(b), C.c_void_p(st.cuda_stream)) != 0:
+                raise RuntimeError("bicg_load_device refused the arrays")
+            return
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         b = np.ascontiguousarray(b, dtype=np.float64)
         lib().bicg_load(self.h, _d(x0), _d(b))
@@ -473,17 +596,42 @@ class Context:
     def sync(self):
         lib().bicg_sync(self.h)
 
-    def fetch(self):
-        x, r = np.zeros(self.n), np.zeros(self.n)
-        lib().bicg_fetch(self.h, _d(x), _d(r))
-        return x, r
+    def fetch(self, device=False, stream=None, x=True, r=True):
+        """(x, r) of the context: numpy arrays (bicg_fetch) or, device=True, CUDA tensors written by bicg_fetch_device on `stream`
+        (default: the current torch stream) without a host wait. x / r: True -- a fresh array; False -- left out (None comes
+        back); a CUDA float64 tensor (implies device=True) -- written in place."""
+        if device or tensor_form(*[t for t in (x, r) if not isinstance(t, bool)]):
+            import torch
+            st = _torch_stream(stream)
+            with torch.cuda.stream(st):
+                out = [torch.empty(self.n, dtype=torch.float64, device="cuda") if t is True else
+                       None if t is False or t is None else _vec1(t, self.n, "fetch", True) for t in (x, r)]
+            if lib().bicg_fetch_device(self.h, _vp(out[0]), _vp(out[1]), C.c_void_p(st.cuda_stream)) != 0:
+                raise RuntimeError("bicg_fetch_device failed")
+            return out[0], out[1]
+        out = [np.zeros(self.n) if t else None for t in (x, r)]
+        lib().bicg_fetch(self.h, *[None if a is None else _d(a) for a in out])
+        return out[0], out[1]
 
     def trace(self, k: int):
         arrs = [np.zeros(max(k, 1)) for _ in range(4)]
         got = lib().bicg_trace(self.h, *[_d(a) for a in arrs])
         return dict(zip(("alpha", "omega", "beta", "dotr"), [a[:got] for a in arrs]))
 
-    def spmv(self, x):
+    def spmv(self, x, out=None, stream=None):
+        """y = A x (collective). A CUDA float64 torch tensor: bicg_spmv_device on `stream` (default: the current torch stream), y a
+        fresh tensor or `out` (not x itself)"""
+        if tensor_form(x, out):
+            import torch
+            st = _torch_stream(stream)
+            with torch.cuda.stream(st):
+                x = _vec1(x, self.n, "x")
+                y = torch.empty(self.n, dtype=torch.float64, device=x.device) if out is None else _vec1(out, self.n, "out", True)
+            if self.n and y.data_ptr() == x.data_ptr():
+                raise ValueError("spmv: out must not be x")
+            if lib().bicg_spmv_device(self.h, _vp(x), _vp(y), C.c_void_p(st.cuda_stream)) != 0:
+                raise RuntimeError("bicg_spmv_device refused the arrays")
+            return y
         x = np.ascontiguousarray(x, dtype=np.float64)
         y = np.zeros(self.n)
         lib().bicg_spmv(self.h, _d(x), _d(y))
