@@ -72,6 +72,12 @@ int bicgstab(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix *A_info
 int ca_bicgstab(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix *A_info, double *x_loc, double *r_loc);
 int pipe_bicgstab(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix *A_info, double *x_loc, double *r_loc);
 int pipe_bicgstab_rr(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix *A_info, double *x_loc, double *r_loc, int krr, int nrr);
+/* Not in the reference: bicgstab() right-preconditioned with M = diag(A) (Jacobi; BICG_BICGSTAB_DIAG, section 3). Same signature,
+ * semantics and printed lines as bicgstab(); r_loc comes back as the recursive residual of A x = b itself, and the stopping test
+ * is bicgstab()'s. The diagonal is read from A_loc_diag (bicg_csr_diagonal, section 5) and installed on the resident drop-in
+ * context by every call -- created, refreshed or reused, and whatever diagonal was installed on it in between. A block in which some row stores no (i,i) entry prints
+ * "Error: matrix has rows without a diagonal entry." to stderr and exit(1); a stored zero is refused the same way. */
+int jacobi_bicgstab(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix *A_info, double *x_loc, double *r_loc);
 
 /* Shifted systems (A + sigma_j I) x_j = b, j = 0..sigma_len-1, solved with ONE Krylov recurrence on
  * the seed system (2 SpMV per iteration whatever the number of shifts) -- all six entry points of
@@ -164,7 +170,8 @@ int bicg_comm_size(void);
  * ------------------------------------------------------------------------------------------- */
 typedef struct bicg_ctx bicg_ctx;
 
-enum { BICG_BICGSTAB = 0, BICG_CA_BICGSTAB = 1, BICG_PIPE_BICGSTAB = 2, BICG_PIPE_BICGSTAB_RR = 3 };
+enum { BICG_BICGSTAB = 0, BICG_CA_BICGSTAB = 1, BICG_PIPE_BICGSTAB = 2, BICG_PIPE_BICGSTAB_RR = 3,
+       BICG_BICGSTAB_DIAG = 4   /* BICG_BICGSTAB right-preconditioned with the diagonal of bicg_precond_diagonal (below) */ };
 
 typedef struct {
     double tol;          /* relative residual tolerance, reference EPS (src/solver.c:3) */
@@ -242,6 +249,40 @@ void bicg_device_free(void *p);
  * Returns 0: done; 1: refused (a list-held value would change), nothing written; -1: NULL context, or a NULL array where entries exist. */
 int bicg_update_values(bicg_ctx *ctx, const double *diag_val, const double *offd_val);               /* host arrays   */
 int bicg_update_values_device(bicg_ctx *ctx, const double *diag_val_d, const double *offd_val_d);    /* device arrays */
+/* (Neither call touches a diagonal preconditioner installed with bicg_precond_diagonal below: a caller whose diagonal changed
+ * installs it again, which costs one launch.) */
+
+/* DIAGONAL PRECONDITIONER, M = diag(d), and the method that uses it. bicg_precond_diagonal installs or replaces it: the context keeps
+ * 1.0 / d[i] on the device -- one correctly rounded division per row and nothing else.
+ *   d            local_rows doubles in the CALLER'S numbering, also on a BICG_FLAG_REORDERED context (it crosses the permutation on
+ *                the device, as the vectors of bicg_load_device do). Any diagonal: diag(A) (bicg_csr_diagonal, section 5), a lumped
+ *                mass matrix, row norms. A rank without rows passes NULL.
+ *   scope        local to the rank: no transport call, bicg_comm_counts does not move. Both variants are synchronised on return; the
+ *                device variant first makes the compute stream wait for `stream` by an event, as the *_device calls below do, so a
+ *                kernel that fills d_d on `stream` right before the call is complete before d_d is read. Not to be called between
+ *                bicg_run_begin and bicg_run_end of ANY solve on the context, whatever its method: the quotients are formed in one
+ *                of the context's work vectors (refused ones, infinities and NaNs among them, stay there until a solve overwrites it).
+ *                Under BICG_GRAPH=1 the captured iteration of method 4 is dropped whenever the array of 1/d is made or freed.
+ *   returns      0 installed; 1 refused -- some d[i] is zero or non-finite (checked on the device by the launch that divides): the
+ *                previous preconditioner, or none, stays in place; -1 NULL context, or a NULL array where rows exist.
+ *   lifetime     the first install allocates local_rows doubles (counted in bicg_device_allocations, released by bicg_destroy or
+ *                bicg_precond_clear); later installs allocate nothing (the host variant's staging buffer is a temporary of the call).
+ * bicg_precond_clear drops it (bicg_device_allocations() is back to what it was before the first install); bicg_precond_kind: 0 none,
+ * 1 diagonal.
+ * BICG_BICGSTAB_DIAG is RIGHT preconditioning: the iteration runs on A M^-1, r stays the residual of the caller's system
+ * A x = b and the stopping test (r,r) > tol^2 (r0,r0) is BICG_BICGSTAB's. The operations are those of reference src/solver.c:74-120
+ * in their order, with p^ = (1/d) o p and q^ = (1/d) o q as the inputs of the two products and in the update of x; with d = 1 the
+ * result is bit-identical to BICG_BICGSTAB's multi-launch form. Accepted by bicg_solve, bicg_run, bicg_run_begin / _iterate /
+ * _iterate_timed / _end and bicg_solve_device; options, result fields, trace, progress and summary lines, breakdown detection and
+ * check_every are BICG_BICGSTAB's. On a context WITHOUT a preconditioner these calls return -2 and touch nothing. Across ranks the
+ * call is collective as for BICG_BICGSTAB; that every rank has installed its part is the caller's contract. It allocates nothing
+ * beyond 1/d: the hat vectors live in work vectors the plain iteration leaves idle.
+ * Out of scope: bicg_solve_multi* keeps refusing every method but BICG_BICGSTAB, and the CA, pipelined and shifted iterations have
+ * no preconditioned form. */
+int bicg_precond_diagonal(bicg_ctx *ctx, const double *d_loc);                       /* host array   */
+int bicg_precond_diagonal_device(bicg_ctx *ctx, const double *d_d, void *stream);    /* device array */
+int bicg_precond_clear(bicg_ctx *ctx);
+int bicg_precond_kind(bicg_ctx *ctx);
 
 /* Matrix residency of the drop-in entry points (section 1 and the shifted ones): the context of the last drop-in call
  * stays resident and is reused when the caller passes the same blocks again -- same arrays, sizes, partition,
@@ -516,6 +557,10 @@ unsigned long long bicg_spmv_matrix_bytes(bicg_ctx *ctx);
  *   bicg_halo_plan   -- unique global columns referenced by an offd block, grouped by owner rank
  * ------------------------------------------------------------------------------------------- */
 void bicg_partition(unsigned int n, int nranks, int *counts, int *displs);
+/* The diagonal of a diag block (local columns): d_out[i] = the stored (i,i) entry, 0.0 where none is stored; a row that stores
+ * (i,i) more than once yields their sum in stored order. Returns the number of rows without one. What bicg_precond_diagonal takes
+ * for a Jacobi preconditioner (after the caller has dealt with the rows that have none). */
+int bicg_csr_diagonal(const CSR_Matrix *diag, double *d_out);
 /* Returns the halo length h and fills (caller-allocated, sizes noted):
  *   halo_cols[offd->nz upper bound]  ascending unique global columns
  *   recv_counts[nranks]              how many of them each rank owns

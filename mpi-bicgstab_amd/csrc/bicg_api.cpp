@@ -77,7 +77,105 @@ void cross_out(bicg_ctx *c, double *user0, const double *dev0, double *user1, co
     launch_vecio(p, np, c->reordered ? c->ro_inv : nullptr, c->n_loc, nvec, c->sc);
 }
 
+// ---- the diagonal preconditioner (bicg_precond_diagonal / _device)
+// d_dev: the caller's d on the device, caller's numbering. One launch writes 1 / d -- through the permutation on a reordered context
+// -- into the context's ax vector and raises the flag for a zero or non-finite entry; only a clean result is copied into dinv, so a
+// refused call leaves what was installed. ax is free between any two calls: every solver writes it (a product's output) before it
+// reads it, and no product takes it as input, so its halo tail does not matter. Synchronised on return.
+// A captured iteration of method 4 (BICG_GRAPH=1, graph_iteration) holds dinv's ADDRESS as an argument of FDiagQ / FDiagP -- the one
+// pointer of a captured iteration that does not live as long as the context. Whenever the array is freed or a new one is made the
+// captured iteration goes too (and its two eager warm-up iterations are due again); an install into the existing array keeps it.
+static void precond_graph_drop(bicg_ctx *c)
+{
+    hipGraphExec_t &g = c->graph_exec[BICG_BICGSTAB_DIAG];
+    if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    c->graph_warm[BICG_BICGSTAB_DIAG] = 0;
+}
+static double *precond_array(bicg_ctx *c)
+{
+    if (!c->dinv) { precond_graph_drop(c); c->dinv = c->own.alloc<double>(c->n_loc); }
+    return c->dinv;
+}
+
+static int precond_install(bicg_ctx *c, const double *d_dev)
+{
+    int flag = 0;
+    launch_dinv(d_dev, c->reordered ? c->ro_perm : nullptr, c->n_loc, c->v.ax, c->refresh_flag, c->sc);
+    BICG_HIP(hipGetLastError());
+    BICG_HIP(hipMemcpyAsync(&flag, c->refresh_flag, sizeof(int), hipMemcpyDeviceToHost, c->sc));
+    BICG_HIP(hipStreamSynchronize(c->sc));
+    if (flag != 0) {                                                   // (zero again for the next call)
+        BICG_HIP(hipMemsetAsync(c->refresh_flag, 0, sizeof(int), c->sc));
+        BICG_HIP(hipStreamSynchronize(c->sc));
+        return 1;
+    }
+    BICG_HIP(hipMemcpyAsync(precond_array(c), c->v.ax, sizeof(double) * c->n_loc, hipMemcpyDeviceToDevice, c->sc));
+    BICG_HIP(hipStreamSynchronize(c->sc));
+    return 0;
+}
+// a rank without rows: its phantom row [1.0] is its own preconditioner
+static int precond_phantom(bicg_ctx *c)
+{
+    const double one = 1.0;
+    BICG_HIP(hipStreamSynchronize(c->sc));
+    BICG_HIP(hipMemcpy(precond_array(c), &one, sizeof one, hipMemcpyHostToDevice));
+    return 0;
+}
+// BICG_BICGSTAB_DIAG on a context without a preconditioner: the solving calls return -2 and touch nothing
+static bool diag_refused(const bicg_ctx *c, int method) { return c && method == BICG_BICGSTAB_DIAG && !c->dinv; }
+
 extern "C" {
+
+int bicg_precond_diagonal(bicg_ctx *c, const double *d_loc)
+{
+    if (!c) return -1;
+    use_device(c);
+    if (c->phantom) return precond_phantom(c);
+    if (!d_loc) return -1;
+    double *stage = dev_alloc<double>(c->n_loc);                       // a temporary of the call, as bicg_update_values' staging
+    BICG_HIP(hipMemcpyAsync(stage, d_loc, sizeof(double) * c->n_loc, hipMemcpyHostToDevice, c->sc));
+    const int rc = precond_install(c, stage);
+    dev_free(stage);
+    return rc;
+}
+
+int bicg_precond_diagonal_device(bicg_ctx *c, const double *d_d, void *stream)
+{
+    if (!c) return -1;
+    use_device(c);
+    if (c->phantom) return precond_phantom(c);
+    if (!d_d) return -1;
+    cross_begin(c, (hipStream_t)stream);      // what the caller enqueued on its stream (the kernel that fills d_d) comes first
+    return precond_install(c, d_d);
+}
+
+int bicg_precond_clear(bicg_ctx *c)
+{
+    if (!c) return -1;
+    if (!c->dinv) return 0;
+    use_device(c);
+    BICG_HIP(hipStreamSynchronize(c->sc));
+    precond_graph_drop(c);
+    c->own.free(c->dinv);
+    c->dinv = nullptr;
+    return 0;
+}
+
+int bicg_precond_kind(bicg_ctx *c) { return c && c->dinv ? 1 : 0; }
+
+int bicg_csr_diagonal(const CSR_Matrix *diag, double *d_out)
+{
+    int missing = 0;
+    for (unsigned i = 0; i < diag->rows; ++i) {
+        bool have = false;
+        double sum = 0.0;
+        for (unsigned k = diag->ptr[i]; k < diag->ptr[i + 1]; ++k)
+            if (diag->col[k] == i) { sum = have ? sum + diag->val[k] : diag->val[k]; have = true; }
+        d_out[i] = have ? sum : 0.0;
+        if (!have) ++missing;
+    }
+    return missing;
+}
 
 int bicg_load_device(bicg_ctx *c, const double *x0_d, const double *b_d, void *stream)
 {
@@ -102,6 +200,7 @@ int bicg_fetch_device(bicg_ctx *c, double *x_d, double *r_d, void *stream)
 int bicg_solve_device(bicg_ctx *c, int method, double *x_d, double *r_d, const bicg_options *opt, bicg_result *res, void *stream)
 {
     if (!c || (!c->phantom && (!x_d || !r_d))) return -1;
+    if (diag_refused(c, method)) return -2;
     bicg_load_device(c, x_d, r_d, stream);
     const int k = run_solver(c, method, opt, res);
     bicg_fetch_device(c, x_d, r_d, stream);
@@ -127,8 +226,17 @@ int bicg_fetch(bicg_ctx *c, double *x, double *r)
     return 0;
 }
 
-int bicg_run(bicg_ctx *c, int method, const bicg_options *opt, bicg_result *res) { return run_solver(c, method, opt, res); }
-int bicg_run_begin(bicg_ctx *c, int method, const bicg_options *opt) { run_begin(c, method, opt); return 0; }
+int bicg_run(bicg_ctx *c, int method, const bicg_options *opt, bicg_result *res)
+{
+    if (diag_refused(c, method)) return -2;
+    return run_solver(c, method, opt, res);
+}
+int bicg_run_begin(bicg_ctx *c, int method, const bicg_options *opt)
+{
+    if (diag_refused(c, method)) return -2;
+    run_begin(c, method, opt);
+    return 0;
+}
 int bicg_run_iterate(bicg_ctx *c, int nsteps) { return run_iterate(c, nsteps); }
 int bicg_run_iterate_timed(bicg_ctx *c, int nsteps, double ms[3])
 {
@@ -156,6 +264,7 @@ int bicg_sync(bicg_ctx *c)
 
 int bicg_solve(bicg_ctx *c, int method, double *x, double *r, const bicg_options *opt, bicg_result *res)
 {
+    if (diag_refused(c, method)) return -2;
     bicg_load(c, x, r);
     const int k = run_solver(c, method, opt, res);
     bicg_fetch(c, x, r);

@@ -612,6 +612,9 @@ void launch_permute_out(const double *src, size_t src_stride, double *dst, size_
 // allow them, one launch when both pairs take the same accesses
 struct VecPair { const double *src; size_t src_ld; double *dst; size_t dst_ld; };
 void launch_vecio(const VecPair *pairs, int npairs, const uint32_t *idx, uint32_t n, int nvec, hipStream_t st);
+// bicg_precond.hip
+// the diagonal preconditioner's install: out[i] = 1.0 / d[perm ? perm[i] : i]; *flag = 1 when some d is zero or non-finite
+void launch_dinv(const double *d, const uint32_t *perm, uint32_t n, double *out, int *flag, hipStream_t st);
 // bicg_refresh.hip
 // new values for the resident matrix (bicg_update_values). RefreshSrc: the caller's values in the CSR order of the block handed to
 // bicg_create; the context's row r starts at val[ptr[rowmap ? rowmap[r] : r]] (rowmap: perm of a reordered context, ptr then the
@@ -670,6 +673,12 @@ void launch_init_residual(const Vecs &v, bool copy_p, bool save_b, const Launch 
 void launch_plain_q(const Vecs &v, const Launch &L);
 void launch_plain_xr(const Vecs &v, const Launch &L, Reduce red, const double *q = nullptr);   // q: where q lives (default: in r)
 void launch_plain_p(const Vecs &v, const Launch &L);
+// diagonally preconditioned BiCGStab: the plain phases with the hat vectors p^ = dinv o p (in v.z) and
+// q^ = dinv o q (in v.w) written by the pass that produces p / q; x takes alpha p^ + omega q^
+void launch_init_residual_diag(const Vecs &v, const double *dinv, const Launch &L, Reduce red);   // ... and p = r, p^ = dinv o p
+void launch_diag_q(const Vecs &v, const double *dinv, const Launch &L);
+void launch_diag_xr(const Vecs &v, const Launch &L, Reduce red);
+void launch_diag_p(const Vecs &v, const double *dinv, const Launch &L);
 // CA-BiCGStab phases (src/solver.c:217-222, 225-228, 233-236 + 240-243)
 void launch_ca_ps(const Vecs &v, const Launch &L);
 void launch_qy(const Vecs &v, const Launch &L, Reduce red);

@@ -177,14 +177,40 @@ bool p2p_fell_back(bicg_ctx *c)
     return true;
 }
 
+// jacobi_bicgstab: diag(A) of the caller's diag block, refused like a matrix that is not square when a row stores none
+std::vector<double> jacobi_diagonal(const CSR_Matrix *diag)
+{
+    std::vector<double> d(std::max<size_t>(diag->rows, 1), 0.0);
+    if (bicg_csr_diagonal(diag, d.data()) != 0) {
+        fprintf(stderr, "Error: matrix has rows without a diagonal entry.\n");
+        exit(1);
+    }
+    return d;
+}
+// ... installed on the resident context by EVERY call: whether the context was created, refreshed or reused by this call does not
+// say whose diagonal it holds -- another drop-in call may have refreshed the values since (BICG_DROPIN_CACHE=2 leaves the
+// preconditioner alone), or the caller may have installed a diagonal of its own on bicg_dropin_context. One upload of a vector and
+// one launch, beside the pass over the whole matrix that dropin_key makes for every call anyway.
+void jacobi_install(bicg_ctx *c, const std::vector<double> &d)
+{
+    if (bicg_precond_diagonal(c, c->phantom ? nullptr : d.data()) != 0) {
+        fprintf(stderr, "Error: matrix has a zero or non-finite diagonal entry.\n");
+        exit(1);
+    }
+}
+
 int dropin(int method, CSR_Matrix *diag, CSR_Matrix *offd, INFO_Matrix *info, double *x, double *r, int krr, int nrr)
 {
     check_square(info);
     bicg_options o;
     env_options(&o);
     o.krr = krr; o.nrr = nrr;
+    const bool jacobi = method == BICG_BICGSTAB_DIAG;
+    std::vector<double> dj;
+    if (jacobi) dj = jacobi_diagonal(diag);
     bicg_ctx *c = dropin_context(diag, offd, info);
     if (!c) die("bicg_create", "failed");
+    if (jacobi) jacobi_install(c, dj);
     bicg_result res;
     // The peer-to-peer data path is chosen automatically when its self-test passes (bicg_comm_init_mpi "auto"). Should it
     // fail in a real solve all the same -- a wait for a peer times out -- the solve is repeated on the transport's own
@@ -197,6 +223,7 @@ int dropin(int method, CSR_Matrix *diag, CSR_Matrix *offd, INFO_Matrix *info, do
         memcpy(r, b.data(), sizeof(double) * b.size());
         c = dropin_context(diag, offd, info);
         if (!c) die("bicg_create", "failed");
+        if (jacobi) jacobi_install(c, dj);
         k = bicg_solve(c, method, x, r, &o, &res);
     }
     dropin_release(c);
@@ -286,6 +313,7 @@ int shifted_lopbicg_switching_noovlp(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *
 
 // ---- drop-in entry points: reference src/solver.h:10-13
 int bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_BICGSTAB, d, o, i, x, r, 0, 0); }
+int jacobi_bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_BICGSTAB_DIAG, d, o, i, x, r, 0, 0); }
 int ca_bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_CA_BICGSTAB, d, o, i, x, r, 0, 0); }
 int pipe_bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_PIPE_BICGSTAB, d, o, i, x, r, 0, 0); }
 int pipe_bicgstab_rr(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r, int krr, int nrr)

@@ -187,6 +187,10 @@ struct bicg_ctx {
     bool inline_apply = true;       // BICG_P2P_INLINE_APPLY=0: always use the separate apply kernel
     int fault_after = 0;            // BICG_TEST="p2p-fault-after=n" (tests): from the n-th exchange on this rank sends nothing
 
+    // diagonal preconditioner (bicg_precond_diagonal; BICG_BICGSTAB_DIAG): 1 / d, n_loc doubles in the
+    // context's numbering; null: none installed. Allocated by the first install, freed by bicg_precond_clear / bicg_destroy
+    double *dinv = nullptr;
+
     // vectors and scalars
     double *slab = nullptr;
     Vecs v{};
@@ -352,9 +356,9 @@ struct bicg_ctx {
 
     // hipGraph replay of the iteration body (BICG_GRAPH): one captured iteration per method
     int graph_mode = -1;                 // -1 auto, 0 off, 1 on
-    hipGraphExec_t graph_exec[4] = {nullptr, nullptr, nullptr, nullptr};
-    int graph_warm[4] = {0, 0, 0, 0};    // eager iterations done since the context was created
-    bool graph_nt[4] = {false, false, false, false};
+    hipGraphExec_t graph_exec[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    int graph_warm[5] = {0, 0, 0, 0, 0};    // eager iterations done since the context was created
+    bool graph_nt[5] = {false, false, false, false, false};
     // now_n > 0: the group is closed by group_now(now_n, phase) right after this producer (not
     // deferred); with the peer-to-peer transport the producer's finishing workgroup then collects
     // and applies it in-kernel and group_now launches nothing.

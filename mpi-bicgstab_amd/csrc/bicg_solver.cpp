@@ -656,6 +656,12 @@ struct Driver {
     {
         const bool plain = method == BICG_BICGSTAB;
         const bool rr = method == BICG_PIPE_BICGSTAB_RR || (method == BICG_PIPE_BICGSTAB && c->opt.rr_drift > 0.0);
+        if (method == BICG_BICGSTAB_DIAG) {
+            spmv(c, v.x, v.ax, 0, nullptr, c->red(0, PH_NONE));                       // Ax = A x0
+            launch_init_residual_diag(v, c->dinv, here(), c->red(0, PH_INIT, true, 1));   // r, r# = r, p = r, p^ = dinv o p, (r,r)
+            group_now(c, 1, PH_INIT);
+            return;
+        }
         if (!c->wave_mode) {
             spmv(c, v.x, v.ax, 0, nullptr, c->red(0, PH_NONE));                       // Ax = A x0
             launch_init_residual(v, plain, rr, here(), c->red(0, PH_INIT, true, 1));  // r = b - Ax, r# = r, (r,r)
@@ -722,6 +728,22 @@ struct Driver {
         launch_plain_xr(v, here(), c->red(0, PH_PLAIN_END, true, 2));    // x, r, (r,r), (r#,r) -> beta, k++
         group_now(c, 2, PH_PLAIN_END);
         launch_plain_p(v, here());                              // p = r + beta (p - omega s)
+    }
+
+    // Right-preconditioned with M = diag(d): iter_plain's operations in its order, the products take the
+    // hat vectors p^ = dinv o p (v.z) and q^ = dinv o q (v.w) -- idle in the plain iteration, zeroed with their halo tails by
+    // run_begin -- and x is updated with them; r stays the residual of the caller's system. Same dot groups and phases, no launch
+    // added; always the multi-launch form with the producer-side finish (no hand-over, no persistent launch).
+    void iter_diag()
+    {
+        spmv(c, v.z, v.s, 1, v.rh, c->red(0, PH_PLAIN_ALPHA, true, 1));   // s = A p^, (r#,s) -> alpha
+        group_now(c, 1, PH_PLAIN_ALPHA);
+        launch_diag_q(v, c->dinv, here());                      // q = r - alpha s ; q^ = dinv o q
+        spmv(c, v.w, v.y, 2, v.r, c->red(0, PH_OMEGA, true, 2));          // y = A q^, (q,y), (y,y) -> omega
+        group_now(c, 2, PH_OMEGA);
+        launch_diag_xr(v, here(), c->red(0, PH_PLAIN_END, true, 2));     // x += alpha p^ + omega q^, r, (r,r), (r#,r) -> beta, k++
+        group_now(c, 2, PH_PLAIN_END);
+        launch_diag_p(v, c->dinv, here());                      // p = r + beta (p - omega s) ; p^ = dinv o p
     }
 
     void iter_ca()      // reference src/solver.c:217-251
@@ -799,6 +821,7 @@ struct Driver {
         switch (method) {
         case BICG_BICGSTAB: iter_plain(); break;
         case BICG_CA_BICGSTAB: iter_ca(); break;
+        case BICG_BICGSTAB_DIAG: iter_diag(); break;
         default: iter_pipe(it, force_replace, last); break;
         }
     }
@@ -861,7 +884,8 @@ void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in)
 {
     bicg_options &o = c->opt;
     if (opt_in) o = *opt_in; else bicg_default_options(&o);
-    if (method < BICG_BICGSTAB || method > BICG_PIPE_BICGSTAB_RR) die("bicg_run", "unknown method");
+    if ((method < BICG_BICGSTAB || method > BICG_PIPE_BICGSTAB_RR) && method != BICG_BICGSTAB_DIAG) die("bicg_run", "unknown method");
+    if (method == BICG_BICGSTAB_DIAG && !c->dinv) die("bicg_run", "BICG_BICGSTAB_DIAG without a preconditioner (bicg_precond_diagonal)");
     if (o.max_iter < 0) o.max_iter = 0;
     if (o.check_every < 1) o.check_every = 1;
     c->method = method;
@@ -870,7 +894,7 @@ void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in)
     // chain at the end of the producer (memory system draining) is then the shortest path. The
     // pipelined solvers defer their groups across an SpMV (src/solver.c:363-367, 377-385): there the sums
     // are staged by that SpMV and finished by the kernel that consumes them, off the critical path.
-    c->wave_mode = method >= BICG_PIPE_BICGSTAB;
+    c->wave_mode = method == BICG_PIPE_BICGSTAB || method == BICG_PIPE_BICGSTAB_RR;
     c->grp = bicg_ctx::Group{};
     c->f1_done = false;
     c->spmv_dir = 0;             // every solve starts in the same direction (its first product toggles this to 1 = reversed):
@@ -881,7 +905,7 @@ void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in)
     // per iteration). Beyond that the matrix only evicts the vectors and is streamed with
     // non-temporal loads instead (Transport, pipelined, 10 vectors: 167.3 vs 173.8 us).
     {
-        static const int nvec[4] = {6, 8, 10, 11};
+        static const int nvec[5] = {6, 8, 10, 11, 9};      // (the preconditioned iteration: the plain one's six, two hat vectors, dinv)
         const double ws = (double)c->matrix_bytes + 8.0 * c->stride * nvec[method];
         // (round 4: with the products alternating direction, ordinary loads pay up to 35 % over the cache -- CA-BiCGStab
         // 166.9 -> 150.6 us per iteration; the pipelined solvers' ten vectors are past that: 157.2 vs 160.9)
@@ -1076,7 +1100,7 @@ int run_iterate(bicg_ctx *c, int nsteps)
     const int stop = std::min(o.max_iter, c->it + std::max(nsteps, 0));
     while (!c->hS->done && c->it < stop) {
         // (section marks are host-side events between launches: the multi-launch forms are what they can time)
-        bool persist = c->persist_on && !c->time_kernels && !c->time_sections && !c->sec_exhausted &&
+        bool persist = c->method != BICG_BICGSTAB_DIAG && c->persist_on && !c->time_kernels && !c->time_sections && !c->sec_exhausted &&
                              ((c->method >= BICG_PIPE_BICGSTAB && (c->persist.rpt == 1u || (c->method == BICG_PIPE_BICGSTAB && o.rr_drift <= 0.0))) ||
                               ((c->method == BICG_BICGSTAB || c->method == BICG_CA_BICGSTAB) && c->persist_plain && c->persist.rpt == 1u) ||
                               ((c->method == BICG_BICGSTAB || c->method == BICG_CA_BICGSTAB) && c->persist_plain && c->persist.rpt == 2u && !c->persist.mat_entries));
@@ -1087,7 +1111,7 @@ int run_iterate(bicg_ctx *c, int nsteps)
         const int chunk = std::min(persist ? std::max(o.check_every, persist_chunk_min) : o.check_every, stop - c->it);
         bool force = false;
         // (the persistent kernel checks the drift itself, every check_every iterations inside the launch)
-        if (!persist && o.rr_drift > 0.0 && c->method >= BICG_PIPE_BICGSTAB && c->it > 0 && d.drift() > o.rr_drift) {
+        if (!persist && o.rr_drift > 0.0 && (c->method == BICG_PIPE_BICGSTAB || c->method == BICG_PIPE_BICGSTAB_RR) && c->it > 0 && d.drift() > o.rr_drift) {
             force = true;
             c->adaptive_rr++;
         }
@@ -1235,7 +1259,7 @@ void probe_pipe_form(bicg_ctx *c, int method, const bicg_options *opt_in)
 
 int run_solver(bicg_ctx *c, int method, const bicg_options *opt_in, bicg_result *res)
 {
-    if (c->pipe_probe && !c->pipe_probed && method >= BICG_PIPE_BICGSTAB) probe_pipe_form(c, method, opt_in);
+    if (c->pipe_probe && !c->pipe_probed && (method == BICG_PIPE_BICGSTAB || method == BICG_PIPE_BICGSTAB_RR)) probe_pipe_form(c, method, opt_in);
     run_begin(c, method, opt_in);
     run_iterate(c, c->opt.max_iter);
     return run_end(c, res);

@@ -429,6 +429,98 @@ struct FPlainP {
 };
 void launch_plain_p(const Vecs &v, const Launch &L) { run_vec(FPlainP{v.p, v.r, v.s, 0.0, 0.0}, v.n, L, Reduce{}); }
 
+// ---- diagonally (right-) preconditioned plain BiCGStab, M = diag(d), dinv = 1 / d: the three phases
+// above with the hat vectors p^ = dinv o p and q^ = dinv o q -- the inputs of the two products -- written by the pass that
+// produces p or q. One rounding per hat entry; with dinv = 1 every phase computes what its plain counterpart computes.
+// init: r = b - Ax ; r# = r ; p = r ; p^ = dinv o p ; (r,r)
+struct FInitDiag {
+    static constexpr int ND = 1;
+    static constexpr int kModes = kAnyMode;
+    double *r, *rh, *p, *ph; const double *ax, *dinv;
+    __device__ void load(const Scal *) {}
+    template <class T> __device__ void apply(uint32_t i, double *acc) const
+    {
+        T rr = ld<T>(r, i) + (-1.0) * ld<T>(ax, i);
+        st(r, i, rr); st(rh, i, rr); st(p, i, rr);
+        st(ph, i, ld<T>(dinv, i) * rr);
+        acc[0] += hsum(rr * rr);
+    }
+};
+void launch_init_residual_diag(const Vecs &v, const double *dinv, const Launch &L, Reduce red)
+{
+    run_vec(FInitDiag{v.r, v.rh, v.p, v.z, v.ax, dinv}, v.n, L, red);
+}
+
+// q = r - alpha s (kept in r) ; q^ = dinv o q
+struct FDiagQ {
+    static constexpr int ND = 0;
+    static constexpr int kModes = kAnyMode;
+    static constexpr bool kSplit = true;
+    double *r, *qh; const double *s, *dinv; double alpha;
+    template <class T> struct In { T r, s, d; };
+    __device__ void load(const Scal *S) { alpha = S->alpha; }
+    template <class T> __device__ In<T> fetch(uint32_t i) const { return {ld<T>(r, i), ld<T>(s, i), ld<T>(dinv, i)}; }
+    template <class T> __device__ void compute(uint32_t i, const In<T> &in, double *) const
+    {
+        T q = in.r + (-alpha) * in.s;
+        st(r, i, q);
+        st(qh, i, in.d * q);
+    }
+    template <class T> __device__ void apply(uint32_t i, double *acc) const { compute<T>(i, fetch<T>(i), acc); }
+};
+void launch_diag_q(const Vecs &v, const double *dinv, const Launch &L) { run_vec(FDiagQ{v.r, v.w, v.s, dinv, 0.0}, v.n, L, Reduce{}); }
+
+// x += alpha p^ + omega q^ ; r = q - omega y ; (r,r), (r#,r)
+template <bool XNT> struct FDiagXR {
+    static constexpr int ND = 2;
+    static constexpr int kModes = kAnyMode;
+    static constexpr bool kSplit = true;
+    double *x, *r; const double *ph, *qh, *y, *rh; double alpha, omega;
+    template <class T> struct In { T q, x, ph, qh, y, rh; };
+    __device__ void load(const Scal *S) { alpha = S->alpha; omega = S->omega; }
+    template <class T> __device__ In<T> fetch(uint32_t i) const
+    {
+        return {ld<T>(r, i), XNT ? ldnt<T>(x, i) : ld<T>(x, i), ld<T>(ph, i), ld<T>(qh, i), ld<T>(y, i), ld<T>(rh, i)};
+    }
+    template <class T> __device__ void compute(uint32_t i, const In<T> &in, double *acc) const
+    {
+        T xx = in.x + alpha * in.ph;
+        xx = xx + omega * in.qh;
+        if (XNT) stnt(x, i, xx); else st(x, i, xx);
+        T rr = in.q + (-omega) * in.y;
+        st(r, i, rr);
+        acc[0] += hsum(rr * rr);
+        acc[1] += hsum(in.rh * rr);
+    }
+    template <class T> __device__ void apply(uint32_t i, double *acc) const { compute<T>(i, fetch<T>(i), acc); }
+};
+void launch_diag_xr(const Vecs &v, const Launch &L, Reduce red)
+{
+    if (stream_x()) run_vec(FDiagXR<true>{v.x, v.r, v.z, v.w, v.y, v.rh, 0.0, 0.0}, v.n, L, red);
+    else run_vec(FDiagXR<false>{v.x, v.r, v.z, v.w, v.y, v.rh, 0.0, 0.0}, v.n, L, red);
+}
+
+// p = beta p ; p += r ; p += (-beta omega) s ; p^ = dinv o p
+struct FDiagP {
+    static constexpr int ND = 0;
+    static constexpr int kModes = kAnyMode;
+    static constexpr bool kSplit = true;
+    double *p, *ph; const double *r, *s, *dinv; double beta, c;
+    template <class T> struct In { T p, r, s, d; };
+    __device__ void load(const Scal *S) { beta = S->beta; c = -S->beta * S->omega; }
+    template <class T> __device__ In<T> fetch(uint32_t i) const { return {ld<T>(p, i), ld<T>(r, i), ld<T>(s, i), ld<T>(dinv, i)}; }
+    template <class T> __device__ void compute(uint32_t i, const In<T> &in, double *) const
+    {
+        T pp = beta * in.p;
+        pp = pp + 1.0 * in.r;
+        pp = pp + c * in.s;
+        st(p, i, pp);
+        st(ph, i, in.d * pp);
+    }
+    template <class T> __device__ void apply(uint32_t i, double *acc) const { compute<T>(i, fetch<T>(i), acc); }
+};
+void launch_diag_p(const Vecs &v, const double *dinv, const Launch &L) { run_vec(FDiagP{v.p, v.z, v.r, v.s, dinv, 0.0, 0.0}, v.n, L, Reduce{}); }
+
 // ---- CA: p = r + beta(p - omega s) ; s = w + beta(s - omega z)         (src/solver.c:217-222)
 struct FCaPS {
     static constexpr int ND = 0;

@@ -18,7 +18,7 @@ from .synth import CSR
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("BICG_HIP_LIB") or os.path.join(PKG_DIR, "libbicgstab_hip.so")
 
-METHODS = {"bicgstab": 0, "ca_bicgstab": 1, "pipe_bicgstab": 2, "pipe_bicgstab_rr": 3}
+METHODS = {"bicgstab": 0, "ca_bicgstab": 1, "pipe_bicgstab": 2, "pipe_bicgstab_rr": 3, "bicgstab_diag": 4}
 
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
@@ -66,6 +66,7 @@ EXPORTS = [
     "bicg_solve_multi", "bicg_multi_trace", "bicg_comm_counts", "bicg_device_allocations",
     "bicg_update_values", "bicg_update_values_device", "bicg_persist_plan_sources", "bicg_dropin_refreshes",
     "bicg_load_device", "bicg_fetch_device", "bicg_solve_device", "bicg_spmv_device", "bicg_solve_multi_device",
+    "bicg_precond_diagonal", "bicg_precond_diagonal_device", "bicg_precond_clear", "bicg_precond_kind", "bicg_csr_diagonal",
 ]
 
 _lib = None
@@ -167,7 +168,15 @@ def lib():
         for fn in (L.bicg_load_device, L.bicg_fetch_device, L.bicg_solve_device, L.bicg_spmv_device, L.bicg_solve_multi_device):
             fn.restype = C.c_int
         L.bicg_persist_plan_sources.argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.c_uint, _up]
-        for name in ("bicgstab", "ca_bicgstab", "pipe_bicgstab"):
+        # diagonal preconditioner
+        L.bicg_precond_diagonal.argtypes = [C.c_void_p, _dp]
+        L.bicg_precond_diagonal_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bicg_precond_clear.argtypes = [C.c_void_p]
+        L.bicg_precond_kind.argtypes = [C.c_void_p]
+        L.bicg_csr_diagonal.argtypes = [C.POINTER(CSRMatrix), _dp]
+        for fn in (L.bicg_precond_diagonal, L.bicg_precond_diagonal_device, L.bicg_precond_clear, L.bicg_precond_kind, L.bicg_csr_diagonal):
+            fn.restype = C.c_int
+        for name in ("bicgstab", "ca_bicgstab", "pipe_bicgstab", "jacobi_bicgstab"):
             getattr(L, name).argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp]
         L.pipe_bicgstab_rr.argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp,
                                        C.c_int, C.c_int]
@@ -393,6 +402,31 @@ class Context:
         o = None if offd_val is None else np.ascontiguousarray(offd_val, dtype=np.float64)
         return int(lib().bicg_update_values(self.h, None if d is None or d.size == 0 else _d(d), None if o is None or o.size == 0 else _d(o)))
 
+    def set_diagonal(self, d, stream=None) -> int:
+        """Install or replace the diagonal preconditioner M = diag(d) for solve("bicgstab_diag") (bicg_precond_diagonal): d as a
+        numpy array or a CUDA float64 torch tensor (bicg_precond_diagonal_device, ordered behind `stream`, default the current
+        torch stream), in the caller's numbering; a rank without rows passes None or an empty array. Returns 0 installed, 1 refused
+        (a zero or non-finite entry; what was installed stays), -1 the array is missing."""
+        if d is not None and tensor_form(d):
+            import torch
+            st = _torch_stream(stream)
+            with torch.cuda.stream(st):
+                d = _vec1(d, self.n, "d")
+            return int(lib().bicg_precond_diagonal_device(self.h, _vp(d), C.c_void_p(st.cuda_stream)))
+        if d is not None:
+            d = np.ascontiguousarray(d, dtype=np.float64)
+            if d.size != self.n:
+                raise ValueError(f"d: {d.size} entries for {self.n} rows")
+        return int(lib().bicg_precond_diagonal(self.h, None if d is None or d.size == 0 else _d(d)))
+
+    def clear_preconditioner(self) -> int:
+        """drop the preconditioner and its device array (bicg_precond_clear)"""
+        return int(lib().bicg_precond_clear(self.h))
+
+    def preconditioner(self):
+        """None, or "diagonal" (bicg_precond_kind)"""
+        return (None, "diagonal")[int(lib().bicg_precond_kind(self.h))]
+
     def close(self):
         if self.h:
             lib().bicg_destroy(self.h)
@@ -571,13 +605,15 @@ class Context:
         kw.setdefault("quiet", 1)
         o = self.options(**kw)
         res = Result()
-        lib().bicg_run(self.h, METHODS[method], C.byref(o), C.byref(res))
+        if lib().bicg_run(self.h, METHODS[method], C.byref(o), C.byref(res)) == -2:
+            raise RuntimeError(f"bicg_run refused method {method!r}: the context has no preconditioner (set_diagonal)")
         return res
 
     def run_begin(self, method: str, **kw):
         kw.setdefault("quiet", 1)
         self._opt = self.options(**kw)
-        lib().bicg_run_begin(self.h, METHODS[method], C.byref(self._opt))
+        if lib().bicg_run_begin(self.h, METHODS[method], C.byref(self._opt)) != 0:      # (nothing was begun: run_iterate would go on with the solve before)
+            raise RuntimeError(f"bicg_run_begin refused method {method!r}: the context has no preconditioner (set_diagonal)")
 
     def run_iterate(self, nsteps: int) -> int:
         return lib().bicg_run_iterate(self.h, nsteps)
@@ -719,6 +755,17 @@ class Context:
         lib().bicg_plan_info(self.h, out)
         return dict(zip(("rows", "nnz_diag", "nnz_offd", "halo", "row_blocks", "boundary_blocks", "sell_rows",
                          "sell_padding"), list(out)))
+
+
+def csr_diagonal(blocks):
+    """(d, missing) of a rank's diag block (bicg_csr_diagonal; blocks: HostBlocks, or a CSR with local columns): d[i] = the stored
+    (i,i) entry -- the sum in stored order where a row stores it more than once --, 0.0 where none is stored; missing = the number
+    of rows without one. No GPU needed."""
+    if isinstance(blocks, CSR):
+        blocks = HostBlocks(blocks, None, blocks.rows, [blocks.rows], [0])
+    d = np.zeros(blocks.n_loc)
+    missing = int(lib().bicg_csr_diagonal(C.byref(blocks.diag), _d(d) if d.size else None))
+    return d, missing
 
 
 def device_allocations() -> int:
