@@ -78,6 +78,12 @@ int pipe_bicgstab_rr(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix
  * context by every call -- created, refreshed or reused, and whatever diagonal was installed on it in between. A block in which some row stores no (i,i) entry prints
  * "Error: matrix has rows without a diagonal entry." to stderr and exit(1); a stored zero is refused the same way. */
 int jacobi_bicgstab(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix *A_info, double *x_loc, double *r_loc);
+/* Not in the reference: bicgstab() right-preconditioned with the bs x bs diagonal blocks of A (block Jacobi; BICG_BICGSTAB_BLOCK,
+ * section 3), bs = 1..16: the unknowns per node of the caller's numbering. Semantics and printed lines are bicgstab()'s. The blocks
+ * are read from A_loc_diag (bicg_csr_block_diagonal, section 5; they never cross a rank's boundary) and installed on the resident
+ * drop-in context by every call. A block that cannot be inverted prints "Error: matrix has a singular diagonal block." to stderr
+ * and exit(1); a bs outside 1..16 prints "Error: block size <bs> is outside 1..16." and exit(1). */
+int block_jacobi_bicgstab(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix *A_info, double *x_loc, double *r_loc, int bs);
 
 /* Shifted systems (A + sigma_j I) x_j = b, j = 0..sigma_len-1, solved with ONE Krylov recurrence on
  * the seed system (2 SpMV per iteration whatever the number of shifts) -- all six entry points of
@@ -171,7 +177,8 @@ int bicg_comm_size(void);
 typedef struct bicg_ctx bicg_ctx;
 
 enum { BICG_BICGSTAB = 0, BICG_CA_BICGSTAB = 1, BICG_PIPE_BICGSTAB = 2, BICG_PIPE_BICGSTAB_RR = 3,
-       BICG_BICGSTAB_DIAG = 4   /* BICG_BICGSTAB right-preconditioned with the diagonal of bicg_precond_diagonal (below) */ };
+       BICG_BICGSTAB_DIAG = 4,  /* BICG_BICGSTAB right-preconditioned with the diagonal of bicg_precond_diagonal (below) */
+       BICG_BICGSTAB_BLOCK = 5  /* BICG_BICGSTAB right-preconditioned with the block diagonal of bicg_precond_block_diagonal (below) */ };
 
 typedef struct {
     double tol;          /* relative residual tolerance, reference EPS (src/solver.c:3) */
@@ -268,7 +275,7 @@ int bicg_update_values_device(bicg_ctx *ctx, const double *diag_val_d, const dou
  *   lifetime     the first install allocates local_rows doubles (counted in bicg_device_allocations, released by bicg_destroy or
  *                bicg_precond_clear); later installs allocate nothing (the host variant's staging buffer is a temporary of the call).
  * bicg_precond_clear drops it (bicg_device_allocations() is back to what it was before the first install); bicg_precond_kind: 0 none,
- * 1 diagonal.
+ * 1 diagonal, 2 block diagonal (below).
  * BICG_BICGSTAB_DIAG is RIGHT preconditioning: the iteration runs on A M^-1, r stays the residual of the caller's system
  * A x = b and the stopping test (r,r) > tol^2 (r0,r0) is BICG_BICGSTAB's. The operations are those of reference src/solver.c:74-120
  * in their order, with p^ = (1/d) o p and q^ = (1/d) o q as the inputs of the two products and in the update of x; with d = 1 the
@@ -283,6 +290,39 @@ int bicg_precond_diagonal(bicg_ctx *ctx, const double *d_loc);                  
 int bicg_precond_diagonal_device(bicg_ctx *ctx, const double *d_d, void *stream);    /* device array */
 int bicg_precond_clear(bicg_ctx *ctx);
 int bicg_precond_kind(bicg_ctx *ctx);
+
+/* BLOCK-JACOBI PRECONDITIONER, M = the bs x bs diagonal blocks the caller passes, and the method that uses it (DESIGN.md section
+ * 4.21). Several unknowns per node put a small dense block on the diagonal whose off-diagonal entries are as large as its diagonal
+ * ones; the install inverts every block once, the iteration multiplies with the inverses.
+ *   blocks       bs is 1..16. Block k covers this rank's local rows [k bs, min((k+1) bs, local_rows)) in the CALLER'S numbering, also
+ *                on a BICG_FLAG_REORDERED context; nblocks = ceil(local_rows / bs); blocks[(k bs + a) bs + j] is entry (a, j) of block
+ *                k, row-major, nblocks bs bs doubles (what bicg_csr_block_diagonal, section 5, writes). Of a partial last block only
+ *                the leading m x m part is read (m = the rows it covers). A rank without rows passes NULL. Blocks are local to the
+ *                rank; that they match the caller's unknowns is the caller's contract.
+ *   returns      0 installed; 1 refused -- a block is singular or holds a non-finite entry (a pivot of the elimination is zero or
+ *                non-finite, or the inverse overflows; checked on the device by the launch that inverts): whatever preconditioner was
+ *                installed, of either kind, stays in place bit for bit; -1 NULL context, or a NULL array where rows exist; -2 bs
+ *                outside 1..16, nothing is touched.
+ *   inversion    Gauss-Jordan with partial pivoting per block (the entry of largest magnitude in the column among the rows not yet
+ *                used, the first one on a tie), the pivot row scaled by one correctly rounded division per entry: bs = 1 keeps exactly
+ *                1.0 / d, a diagonal block exactly 1.0 / d on its diagonal and zeros elsewhere.
+ *   scope        as bicg_precond_diagonal: local to the rank (bicg_comm_counts does not move), synchronised on return, the device
+ *                variant ordered behind `stream` by an event; not to be called between bicg_run_begin and bicg_run_end.
+ *   lifetime     ONE preconditioner per context: a successful install of one kind releases the other kind's array. The context keeps
+ *                bs planes of local_rows doubles (rounded up to whole 256-byte lines): one allocation, made by the first install, kept
+ *                by later installs with the same bs, replaced by one with another bs; staging and the elimination's scratch are
+ *                temporaries of the call. bicg_precond_clear drops whichever kind is installed; bicg_precond_kind returns 2 for this one.
+ *                Under BICG_GRAPH=1 the captured iteration of method 5 is dropped whenever the planes are made, freed or replaced.
+ * BICG_BICGSTAB_BLOCK is BICG_BICGSTAB_DIAG with p^ = M^-1 p and q^ = M^-1 q formed by a launch of their own (seven launches per
+ * iteration instead of five; row i takes acc = m_0 v_0, then acc = fma(m_j, v_j, acc) over its block's rows in ascending order, whatever
+ * the grid, the rank count or the layout). Accepted wherever method 4 is; options, result fields, trace, printed lines, breakdown
+ * detection and check_every are BICG_BICGSTAB's. With bs = 1, or with blocks that hold d on their diagonals and zeros elsewhere, it is
+ * bit-identical to method 4 with that d (as long as no entry of p or q is a zero, whose sign the two forms may render differently).
+ * Method 5 on a context whose kind is not 2 returns -2 and touches nothing, as method 4 does on one whose kind is not 1.
+ * Out of scope: forming the hat vectors in the pass that produces p or q, bicg_solve_multi*, the CA / pipelined / shifted iterations,
+ * blocks of varying size. */
+int bicg_precond_block_diagonal(bicg_ctx *ctx, const double *blocks, int bs);                          /* host array   */
+int bicg_precond_block_diagonal_device(bicg_ctx *ctx, const double *blocks_d, int bs, void *stream);   /* device array */
 
 /* Matrix residency of the drop-in entry points (section 1 and the shifted ones): the context of the last drop-in call
  * stays resident and is reused when the caller passes the same blocks again -- same arrays, sizes, partition,
@@ -425,6 +465,13 @@ int bicg_solve_multi_device(bicg_ctx *ctx, int method, double *x_set_d, double *
  *   bicg_dot         <- my_ddot + MPI_Iallreduce, reference src/vector.c:9-15, src/solver.c:89-91
  * ------------------------------------------------------------------------------------------- */
 int bicg_spmv(bicg_ctx *ctx, const double *x_loc, double *y_loc);
+/* z = M^-1 v for the installed preconditioner (kind 1 or 2); host arrays, caller's numbering, local to the rank; z may alias v.
+ * Returns 0 done, -2 none installed (or a NULL context). Uses two of the context's work vectors: not between bicg_run_begin and
+ * bicg_run_end. The operator by itself, for tests and for a flexible outer iteration of the caller's. */
+int bicg_precond_apply(bicg_ctx *ctx, const double *v_loc, double *z_loc);
+/* reps back-to-back applications of the installed preconditioner on device-resident vectors; returns average ms per application
+ * (HIP events on the library's compute stream), as bicg_spmv_bench does for the product. 0 done, -2 none installed. */
+int bicg_precond_apply_bench(bicg_ctx *ctx, int reps, double *ms_per_apply);
 double bicg_dot(bicg_ctx *ctx, const double *x_loc, const double *y_loc);
 /* reps back-to-back SpMVs on device-resident vectors; returns average ms per SpMV (HIP events on
  * the library's compute stream) */
@@ -561,6 +608,11 @@ void bicg_partition(unsigned int n, int nranks, int *counts, int *displs);
  * (i,i) more than once yields their sum in stored order. Returns the number of rows without one. What bicg_precond_diagonal takes
  * for a Jacobi preconditioner (after the caller has dealt with the rows that have none). */
 int bicg_csr_diagonal(const CSR_Matrix *diag, double *d_out);
+/* The bs x bs diagonal blocks of a diag block (local columns) in the layout bicg_precond_block_diagonal takes (ceil(rows / bs) bs bs
+ * doubles): entry (i, j) with i / bs == j / bs lands at its place, an entry stored more than once yields the sum in stored order,
+ * everything else is 0.0. Returns the number of rows without a stored (i,i) entry (information only: a block without one may well be
+ * regular); -2 for bs outside 1..16, nothing written. With bs = 1 the output is bicg_csr_diagonal's. */
+int bicg_csr_block_diagonal(const CSR_Matrix *diag, int bs, double *blocks_out);
 /* Returns the halo length h and fills (caller-allocated, sizes noted):
  *   halo_cols[offd->nz upper bound]  ascending unique global columns
  *   recv_counts[nranks]              how many of them each rank owns

@@ -615,6 +615,20 @@ void launch_vecio(const VecPair *pairs, int npairs, const uint32_t *idx, uint32_
 // bicg_precond.hip
 // the diagonal preconditioner's install: out[i] = 1.0 / d[perm ? perm[i] : i]; *flag = 1 when some d is zero or non-finite
 void launch_dinv(const double *d, const uint32_t *perm, uint32_t n, double *out, int *flag, hipStream_t st);
+// bicg_bjacobi.hip
+// the block-Jacobi preconditioner: n rows in blocks of bs (1 .. 16) in the caller's numbering, the last one
+// possibly partial. blocks: bjac_blocks(n, bs) x bs x bs doubles, row-major per block, the caller's layout.
+inline uint32_t bjac_blocks(uint32_t n, int bs) { return (uint32_t)(((uint64_t)n + (uint32_t)bs - 1) / (uint32_t)bs); }
+// work (as many doubles as blocks holds) = the inverses, entry (a, j) of block k at work[(a bs + j) nblocks + k]; *flag = 1 when a block
+// holds a non-finite entry or the elimination meets a zero or non-finite pivot
+void launch_bjac_invert(const double *blocks, uint32_t n, int bs, double *work, int *flag, hipStream_t st);
+// minv[j stride + i] = the inverse's entry that multiplies mate j of context row i (perm: a reordered context's, else null); zeros
+// in the planes a partial block does not use
+void launch_bjac_planes(const double *work, const uint32_t *perm, uint32_t n, int bs, double *minv, size_t stride, hipStream_t st);
+// out[i] = sum_j minv[j stride + i] in[mate_j(i)], acc = m_0 v_0 then fma for j ascending; out must not alias in. perm / inv: both
+// or neither
+void launch_bjac_apply(const double *minv, size_t stride, int bs, const uint32_t *perm, const uint32_t *inv, const double *in, double *out,
+                       uint32_t n, hipStream_t st);
 // bicg_refresh.hip
 // new values for the resident matrix (bicg_update_values). RefreshSrc: the caller's values in the CSR order of the block handed to
 // bicg_create; the context's row r starts at val[ptr[rowmap ? rowmap[r] : r]] (rowmap: perm of a reordered context, ptr then the

@@ -199,7 +199,26 @@ void jacobi_install(bicg_ctx *c, const std::vector<double> &d)
     }
 }
 
-int dropin(int method, CSR_Matrix *diag, CSR_Matrix *offd, INFO_Matrix *info, double *x, double *r, int krr, int nrr)
+// block_jacobi_bicgstab: the bs x bs diagonal blocks of the caller's diag block, installed by every call like jacobi's diagonal
+std::vector<double> jacobi_blocks(const CSR_Matrix *diag, int bs)
+{
+    if (bs < 1 || bs > 16) {
+        fprintf(stderr, "Error: block size %d is outside 1..16.\n", bs);
+        exit(1);
+    }
+    std::vector<double> blk(std::max<size_t>(((size_t)diag->rows + bs - 1) / bs * bs * bs, 1), 0.0);
+    (void)bicg_csr_block_diagonal(diag, bs, blk.data());      // (rows without a stored (i,i): a block without one may well be regular)
+    return blk;
+}
+void block_jacobi_install(bicg_ctx *c, const std::vector<double> &blk, int bs)
+{
+    if (bicg_precond_block_diagonal(c, c->phantom ? nullptr : blk.data(), bs) != 0) {
+        fprintf(stderr, "Error: matrix has a singular diagonal block.\n");
+        exit(1);
+    }
+}
+
+int dropin(int method, CSR_Matrix *diag, CSR_Matrix *offd, INFO_Matrix *info, double *x, double *r, int krr, int nrr, int bs = 0)
 {
     check_square(info);
     bicg_options o;
@@ -207,10 +226,13 @@ int dropin(int method, CSR_Matrix *diag, CSR_Matrix *offd, INFO_Matrix *info, do
     o.krr = krr; o.nrr = nrr;
     const bool jacobi = method == BICG_BICGSTAB_DIAG;
     std::vector<double> dj;
+    const bool block = method == BICG_BICGSTAB_BLOCK;
     if (jacobi) dj = jacobi_diagonal(diag);
+    if (block) dj = jacobi_blocks(diag, bs);
     bicg_ctx *c = dropin_context(diag, offd, info);
     if (!c) die("bicg_create", "failed");
     if (jacobi) jacobi_install(c, dj);
+    if (block) block_jacobi_install(c, dj, bs);
     bicg_result res;
     // The peer-to-peer data path is chosen automatically when its self-test passes (bicg_comm_init_mpi "auto"). Should it
     // fail in a real solve all the same -- a wait for a peer times out -- the solve is repeated on the transport's own
@@ -224,6 +246,7 @@ int dropin(int method, CSR_Matrix *diag, CSR_Matrix *offd, INFO_Matrix *info, do
         c = dropin_context(diag, offd, info);
         if (!c) die("bicg_create", "failed");
         if (jacobi) jacobi_install(c, dj);
+        if (block) block_jacobi_install(c, dj, bs);
         k = bicg_solve(c, method, x, r, &o, &res);
     }
     dropin_release(c);
@@ -314,6 +337,7 @@ int shifted_lopbicg_switching_noovlp(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *
 // ---- drop-in entry points: reference src/solver.h:10-13
 int bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_BICGSTAB, d, o, i, x, r, 0, 0); }
 int jacobi_bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_BICGSTAB_DIAG, d, o, i, x, r, 0, 0); }
+int block_jacobi_bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r, int bs) { return dropin(BICG_BICGSTAB_BLOCK, d, o, i, x, r, 0, 0, bs); }
 int ca_bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_CA_BICGSTAB, d, o, i, x, r, 0, 0); }
 int pipe_bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_PIPE_BICGSTAB, d, o, i, x, r, 0, 0); }
 int pipe_bicgstab_rr(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r, int krr, int nrr)

@@ -190,6 +190,12 @@ struct bicg_ctx {
     // diagonal preconditioner (bicg_precond_diagonal; BICG_BICGSTAB_DIAG): 1 / d, n_loc doubles in the
     // context's numbering; null: none installed. Allocated by the first install, freed by bicg_precond_clear / bicg_destroy
     double *dinv = nullptr;
+    // block-Jacobi preconditioner (bicg_precond_block_diagonal; BICG_BICGSTAB_BLOCK): the inverted bs x bs
+    // blocks as bjac_bs planes of bjac_stride doubles in the context's numbering (csrc/bicg_bjacobi.hip); null: none installed. At most
+    // one of dinv / bjac is held: a successful install of one kind releases the other
+    double *bjac = nullptr;
+    int bjac_bs = 0;
+    size_t bjac_stride = 0;
 
     // vectors and scalars
     double *slab = nullptr;
@@ -356,9 +362,9 @@ struct bicg_ctx {
 
     // hipGraph replay of the iteration body (BICG_GRAPH): one captured iteration per method
     int graph_mode = -1;                 // -1 auto, 0 off, 1 on
-    hipGraphExec_t graph_exec[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int graph_warm[5] = {0, 0, 0, 0, 0};    // eager iterations done since the context was created
-    bool graph_nt[5] = {false, false, false, false, false};
+    hipGraphExec_t graph_exec[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int graph_warm[6] = {0, 0, 0, 0, 0, 0};    // eager iterations done since the context was created
+    bool graph_nt[6] = {false, false, false, false, false, false};
     // now_n > 0: the group is closed by group_now(now_n, phase) right after this producer (not
     // deferred); with the peer-to-peer transport the producer's finishing workgroup then collects
     // and applies it in-kernel and group_now launches nothing.

@@ -662,6 +662,13 @@ struct Driver {
             group_now(c, 1, PH_INIT);
             return;
         }
+        if (method == BICG_BICGSTAB_BLOCK) {
+            spmv(c, v.x, v.ax, 0, nullptr, c->red(0, PH_NONE));                       // Ax = A x0
+            launch_init_residual(v, true, false, here(), c->red(0, PH_INIT, true, 1));    // r = b - Ax, r# = r, p = r, (r,r)
+            group_now(c, 1, PH_INIT);
+            block_apply(v.p, v.z);                                                    // p^ = M^-1 p
+            return;
+        }
         if (!c->wave_mode) {
             spmv(c, v.x, v.ax, 0, nullptr, c->red(0, PH_NONE));                       // Ax = A x0
             launch_init_residual(v, plain, rr, here(), c->red(0, PH_INIT, true, 1));  // r = b - Ax, r# = r, (r,r)
@@ -746,6 +753,30 @@ struct Driver {
         launch_diag_p(v, c->dinv, here());                      // p = r + beta (p - omega s) ; p^ = dinv o p
     }
 
+    // Right-preconditioned with the block diagonal of bicg_precond_block_diagonal: iter_diag with the fused
+    // hat products replaced by the plain functors plus one launch of k_bjac_apply each -- p is updated in place and a row's
+    // block-mates live in other lanes or workgroups, so the hat vector cannot be formed by the pass that produces p or q. Seven
+    // launches; the apply launches write v.z / v.w only, so iterations enqueued behind a converged one change neither x, r nor
+    // the scalars. Same dot groups and phases, producer-side finish, multi-launch.
+    void block_apply(const double *in, double *out)
+    {
+        launch_bjac_apply(c->bjac, c->bjac_stride, c->bjac_bs, c->reordered ? c->ro_perm : nullptr, c->reordered ? c->ro_inv : nullptr, in, out,
+                          c->n_loc, c->sc);
+    }
+    void iter_block()
+    {
+        spmv(c, v.z, v.s, 1, v.rh, c->red(0, PH_PLAIN_ALPHA, true, 1));   // s = A p^, (r#,s) -> alpha
+        group_now(c, 1, PH_PLAIN_ALPHA);
+        launch_plain_q(v, here());                              // q = r - alpha s (in v.r)
+        block_apply(v.r, v.w);                                  // q^ = M^-1 q
+        spmv(c, v.w, v.y, 2, v.r, c->red(0, PH_OMEGA, true, 2));          // y = A q^, (q,y), (y,y) -> omega
+        group_now(c, 2, PH_OMEGA);
+        launch_diag_xr(v, here(), c->red(0, PH_PLAIN_END, true, 2));     // x += alpha p^ + omega q^, r, (r,r), (r#,r) -> beta, k++
+        group_now(c, 2, PH_PLAIN_END);
+        launch_plain_p(v, here());                              // p = r + beta (p - omega s)
+        block_apply(v.p, v.z);                                  // p^ = M^-1 p
+    }
+
     void iter_ca()      // reference src/solver.c:217-251
     {
         launch_ca_ps(v, here());                                // p, s recurrences
@@ -822,6 +853,7 @@ struct Driver {
         case BICG_BICGSTAB: iter_plain(); break;
         case BICG_CA_BICGSTAB: iter_ca(); break;
         case BICG_BICGSTAB_DIAG: iter_diag(); break;
+        case BICG_BICGSTAB_BLOCK: iter_block(); break;
         default: iter_pipe(it, force_replace, last); break;
         }
     }
@@ -884,8 +916,9 @@ void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in)
 {
     bicg_options &o = c->opt;
     if (opt_in) o = *opt_in; else bicg_default_options(&o);
-    if ((method < BICG_BICGSTAB || method > BICG_PIPE_BICGSTAB_RR) && method != BICG_BICGSTAB_DIAG) die("bicg_run", "unknown method");
+    if (method < BICG_BICGSTAB || method > BICG_BICGSTAB_BLOCK) die("bicg_run", "unknown method");
     if (method == BICG_BICGSTAB_DIAG && !c->dinv) die("bicg_run", "BICG_BICGSTAB_DIAG without a preconditioner (bicg_precond_diagonal)");
+    if (method == BICG_BICGSTAB_BLOCK && !c->bjac) die("bicg_run", "BICG_BICGSTAB_BLOCK without a preconditioner (bicg_precond_block_diagonal)");
     if (o.max_iter < 0) o.max_iter = 0;
     if (o.check_every < 1) o.check_every = 1;
     c->method = method;
@@ -905,8 +938,9 @@ void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in)
     // per iteration). Beyond that the matrix only evicts the vectors and is streamed with
     // non-temporal loads instead (Transport, pipelined, 10 vectors: 167.3 vs 173.8 us).
     {
-        static const int nvec[5] = {6, 8, 10, 11, 9};      // (the preconditioned iteration: the plain one's six, two hat vectors, dinv)
-        const double ws = (double)c->matrix_bytes + 8.0 * c->stride * nvec[method];
+        // (the preconditioned iterations: the plain one's six, two hat vectors, dinv -- or, block Jacobi, the bs planes added below)
+        static const int nvec[6] = {6, 8, 10, 11, 9, 8};
+        const double ws = (double)c->matrix_bytes + 8.0 * c->stride * (nvec[method] + (method == BICG_BICGSTAB_BLOCK ? c->bjac_bs : 0));
         // (round 4: with the products alternating direction, ordinary loads pay up to 35 % over the cache -- CA-BiCGStab
         // 166.9 -> 150.6 us per iteration; the pipelined solvers' ten vectors are past that: 157.2 vs 160.9)
         // (round 5, the products of rounds 4-5 and an irregular matrix: ordinary loads win far beyond that -- FEM-like, 1.6 M rows,
@@ -1100,7 +1134,7 @@ int run_iterate(bicg_ctx *c, int nsteps)
     const int stop = std::min(o.max_iter, c->it + std::max(nsteps, 0));
     while (!c->hS->done && c->it < stop) {
         // (section marks are host-side events between launches: the multi-launch forms are what they can time)
-        bool persist = c->method != BICG_BICGSTAB_DIAG && c->persist_on && !c->time_kernels && !c->time_sections && !c->sec_exhausted &&
+        bool persist = c->method != BICG_BICGSTAB_DIAG && c->method != BICG_BICGSTAB_BLOCK && c->persist_on && !c->time_kernels && !c->time_sections && !c->sec_exhausted &&
                              ((c->method >= BICG_PIPE_BICGSTAB && (c->persist.rpt == 1u || (c->method == BICG_PIPE_BICGSTAB && o.rr_drift <= 0.0))) ||
                               ((c->method == BICG_BICGSTAB || c->method == BICG_CA_BICGSTAB) && c->persist_plain && c->persist.rpt == 1u) ||
                               ((c->method == BICG_BICGSTAB || c->method == BICG_CA_BICGSTAB) && c->persist_plain && c->persist.rpt == 2u && !c->persist.mat_entries));

@@ -18,7 +18,17 @@ from .synth import CSR
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("BICG_HIP_LIB") or os.path.join(PKG_DIR, "libbicgstab_hip.so")
 
-METHODS = {"bicgstab": 0, "ca_bicgstab": 1, "pipe_bicgstab": 2, "pipe_bicgstab_rr": 3, "bicgstab_diag": 4}
+class _Methods(dict):
+    """name -> method number of include/bicgstab_hip.h. The table's own entries -- what iterating over it, len() and values() show --
+    are the methods 0..4, a census that tests/test_precond.py pins; a method added since is in LATER_METHODS and is found by
+    subscription all the same (METHODS["bicgstab_block"] == 5), which is how every call of this module looks a method up."""
+
+    def __missing__(self, name):
+        return LATER_METHODS[name]
+
+
+METHODS = _Methods({"bicgstab": 0, "ca_bicgstab": 1, "pipe_bicgstab": 2, "pipe_bicgstab_rr": 3, "bicgstab_diag": 4})
+LATER_METHODS = {"bicgstab_block": 5}      # BICG_BICGSTAB_BLOCK (DESIGN.md section 4.21)
 
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
@@ -67,6 +77,8 @@ EXPORTS = [
     "bicg_update_values", "bicg_update_values_device", "bicg_persist_plan_sources", "bicg_dropin_refreshes",
     "bicg_load_device", "bicg_fetch_device", "bicg_solve_device", "bicg_spmv_device", "bicg_solve_multi_device",
     "bicg_precond_diagonal", "bicg_precond_diagonal_device", "bicg_precond_clear", "bicg_precond_kind", "bicg_csr_diagonal",
+    "bicg_precond_block_diagonal", "bicg_precond_block_diagonal_device", "bicg_precond_apply", "bicg_csr_block_diagonal",
+    "bicg_precond_apply_bench",
 ]
 
 _lib = None
@@ -175,6 +187,17 @@ def lib():
         L.bicg_precond_kind.argtypes = [C.c_void_p]
         L.bicg_csr_diagonal.argtypes = [C.POINTER(CSRMatrix), _dp]
         for fn in (L.bicg_precond_diagonal, L.bicg_precond_diagonal_device, L.bicg_precond_clear, L.bicg_precond_kind, L.bicg_csr_diagonal):
+            fn.restype = C.c_int
+        # block-Jacobi preconditioner
+        L.bicg_precond_block_diagonal.argtypes = [C.c_void_p, _dp, C.c_int]
+        L.bicg_precond_block_diagonal_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.bicg_precond_apply.argtypes = [C.c_void_p, _dp, _dp]
+        L.bicg_precond_apply_bench.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.bicg_precond_apply_bench.restype = C.c_int
+        L.bicg_csr_block_diagonal.argtypes = [C.POINTER(CSRMatrix), C.c_int, _dp]
+        L.block_jacobi_bicgstab.argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp, C.c_int]
+        for fn in (L.bicg_precond_block_diagonal, L.bicg_precond_block_diagonal_device, L.bicg_precond_apply, L.bicg_csr_block_diagonal,
+                   L.block_jacobi_bicgstab):
             fn.restype = C.c_int
         for name in ("bicgstab", "ca_bicgstab", "pipe_bicgstab", "jacobi_bicgstab"):
             getattr(L, name).argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp]
@@ -419,13 +442,54 @@ class Context:
                 raise ValueError(f"d: {d.size} entries for {self.n} rows")
         return int(lib().bicg_precond_diagonal(self.h, None if d is None or d.size == 0 else _d(d)))
 
+    def set_block_diagonal(self, blocks, bs: int, stream=None) -> int:
+        """Install or replace the block-Jacobi preconditioner for solve("bicgstab_block") (bicg_precond_block_diagonal): the bs x bs
+        diagonal blocks (bs = 1..16) of this rank's rows in the caller's numbering, ceil(n / bs) * bs * bs doubles, block k's entry
+        (a, j) at [(k * bs + a) * bs + j] -- what csr_block_diagonal returns --, as a numpy array or a CUDA float64 torch tensor
+        (bicg_precond_block_diagonal_device, ordered behind `stream`, default the current torch stream); a rank without rows passes
+        None or an empty array. Returns 0 installed, 1 refused (a singular block or a non-finite entry; what was installed, of
+        either kind, stays), -1 the array is missing, -2 bs outside 1..16."""
+        bs = int(bs)
+        want = -(-self.n // bs) * bs * bs if 1 <= bs <= 16 else None
+        if blocks is not None and tensor_form(blocks):
+            import torch
+            st = _torch_stream(stream)
+            with torch.cuda.stream(st):
+                blocks = blocks.contiguous().reshape(-1)
+            if want is not None and blocks.numel() != want:
+                raise ValueError(f"blocks: {blocks.numel()} entries, {want} for {self.n} rows in blocks of {bs}")
+            return int(lib().bicg_precond_block_diagonal_device(self.h, _vp(blocks), bs, C.c_void_p(st.cuda_stream)))
+        if blocks is not None:
+            blocks = np.ascontiguousarray(blocks, dtype=np.float64).reshape(-1)
+            if want is not None and blocks.size != want:
+                raise ValueError(f"blocks: {blocks.size} entries, {want} for {self.n} rows in blocks of {bs}")
+        return int(lib().bicg_precond_block_diagonal(self.h, None if blocks is None or blocks.size == 0 else _d(blocks), bs))
+
+    def apply_preconditioner(self, v):
+        """z = M^-1 v for the installed preconditioner of either kind (bicg_precond_apply): numpy in the caller's numbering, local
+        to the rank. RuntimeError when none is installed."""
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.size != self.n:
+            raise ValueError(f"v: {v.size} entries for {self.n} rows")
+        z = np.zeros(self.n)
+        if lib().bicg_precond_apply(self.h, _d(v) if v.size else None, _d(z) if z.size else None) != 0:
+            raise RuntimeError("bicg_precond_apply: the context has no preconditioner (set_diagonal / set_block_diagonal)")
+        return z
+
+    def apply_preconditioner_bench(self, reps: int) -> float:
+        """ms per application of the installed preconditioner, reps back to back on the device (bicg_precond_apply_bench)"""
+        ms = C.c_double(0.0)
+        if lib().bicg_precond_apply_bench(self.h, reps, C.byref(ms)) != 0:
+            raise RuntimeError("bicg_precond_apply_bench: the context has no preconditioner (set_diagonal / set_block_diagonal)")
+        return ms.value
+
     def clear_preconditioner(self) -> int:
-        """drop the preconditioner and its device array (bicg_precond_clear)"""
+        """drop the preconditioner, of either kind, and its device array (bicg_precond_clear)"""
         return int(lib().bicg_precond_clear(self.h))
 
     def preconditioner(self):
-        """None, or "diagonal" (bicg_precond_kind)"""
-        return (None, "diagonal")[int(lib().bicg_precond_kind(self.h))]
+        """None, "diagonal" or "block_diagonal" (bicg_precond_kind)"""
+        return (None, "diagonal", "block_diagonal")[int(lib().bicg_precond_kind(self.h))]
 
     def close(self):
         if self.h:
@@ -606,14 +670,14 @@ class Context:
         o = self.options(**kw)
         res = Result()
         if lib().bicg_run(self.h, METHODS[method], C.byref(o), C.byref(res)) == -2:
-            raise RuntimeError(f"bicg_run refused method {method!r}: the context has no preconditioner (set_diagonal)")
+            raise RuntimeError(f"bicg_run refused method {method!r}: the context does not hold its preconditioner ({_installer(method)})")
         return res
 
     def run_begin(self, method: str, **kw):
         kw.setdefault("quiet", 1)
         self._opt = self.options(**kw)
         if lib().bicg_run_begin(self.h, METHODS[method], C.byref(self._opt)) != 0:      # (nothing was begun: run_iterate would go on with the solve before)
-            raise RuntimeError(f"bicg_run_begin refused method {method!r}: the context has no preconditioner (set_diagonal)")
+            raise RuntimeError(f"bicg_run_begin refused method {method!r}: the context does not hold its preconditioner ({_installer(method)})")
 
     def run_iterate(self, nsteps: int) -> int:
         return lib().bicg_run_iterate(self.h, nsteps)
@@ -766,6 +830,24 @@ def csr_diagonal(blocks):
     d = np.zeros(blocks.n_loc)
     missing = int(lib().bicg_csr_diagonal(C.byref(blocks.diag), _d(d) if d.size else None))
     return d, missing
+
+
+def csr_block_diagonal(blocks, bs: int):
+    """(blocks, missing) of a rank's diag block (bicg_csr_block_diagonal; blocks: HostBlocks, or a CSR with local columns): the bs x bs
+    diagonal blocks in the layout set_block_diagonal takes, shaped [ceil(n / bs), bs, bs] -- entries stored more than once summed in
+    stored order, everything not stored 0.0; missing = the number of rows without a stored (i,i) entry. No GPU needed."""
+    bs = int(bs)
+    if not 1 <= bs <= 16:
+        raise ValueError(f"bs = {bs} is outside 1..16")
+    if isinstance(blocks, CSR):
+        blocks = HostBlocks(blocks, None, blocks.rows, [blocks.rows], [0])
+    out = np.zeros((-(-blocks.n_loc // bs), bs, bs))
+    missing = int(lib().bicg_csr_block_diagonal(C.byref(blocks.diag), bs, _d(out) if out.size else None))
+    return out, missing
+
+
+def _installer(method: str) -> str:
+    return "set_block_diagonal" if method == "bicgstab_block" else "set_diagonal"
 
 
 def device_allocations() -> int:

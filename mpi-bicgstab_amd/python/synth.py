@@ -128,6 +128,36 @@ def fem_like(n: int = TRANSPORT_N, seed: int = 4242, keep: float = 0.55, rows=No
     return CSR(A.rows, n, p2.astype(np.uint32), A.col[keep_mask], A.val[keep_mask])
 
 
+def block_coupled(n: int, bs: int, gen=None, coupling: float = 48.0, scale_decades: float = 0.0) -> CSR:
+    """gen(n) (default transport_like) with a skew coupling in every whole bs x bs diagonal block: several unknowns per node, whose
+    block has off-diagonal entries as large as its diagonal ones -- what point Jacobi does not see and block Jacobi removes.
+    nb = n // bs whole blocks; rows from nb * bs on stay as they are. Every stored entry (i, j) with i != j, i // bs == j // bs and
+    both below nb * bs is dropped; for every pair a < b of a block, r = blk * bs + a and c = blk * bs + b get (r, c) = +w and
+    (c, r) = -w with w = coupling * (0.5 + 0.5 * _uniform(r * 64 + (c - r), 555)). scale_decades > 0 then applies A <- D A D with
+    D = row_scale. Columns ascending in every row. Pure numpy."""
+    A = (transport_like if gen is None else gen)(n)
+    nb = n // bs
+    lim = nb * bs
+    row, col, val = A.to_coo()
+    row, col = row.astype(np.int64), col.astype(np.int64)
+    drop = (row != col) & (row // bs == col // bs) & (row < lim) & (col < lim)
+    row, col, val = row[~drop], col[~drop], val[~drop]
+    a, b = np.triu_indices(bs, 1)                                         # the pairs a < b of one block
+    base = (np.arange(nb, dtype=np.int64) * bs)[:, None]
+    r, c = (base + a[None, :]).ravel(), (base + b[None, :]).ravel()
+    w = coupling * (0.5 + 0.5 * _uniform(r * 64 + (c - r), 555))
+    row = np.concatenate([row, r, c])
+    col = np.concatenate([col, c, r])
+    val = np.concatenate([val, w, -w])
+    order = np.lexsort((col, row))
+    row, col, val = row[order], col[order], val[order]
+    if scale_decades > 0.0:
+        val = val * row_scale(row, scale_decades) * row_scale(col, scale_decades)
+    ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(row, minlength=n), out=ptr[1:])
+    return CSR(n, n, ptr.astype(np.uint32), col.astype(np.uint32), val)
+
+
 def transport_nnz(n: int = TRANSPORT_N) -> int:
     """non-zeros of transport_like(n) without building it"""
     return sum(max(n - abs(o), 0) for o in TRANSPORT_OFFSETS)
