@@ -77,232 +77,7 @@ void cross_out(bicg_ctx *c, double *user0, const double *dev0, double *user1, co
     launch_vecio(p, np, c->reordered ? c->ro_inv : nullptr, c->n_loc, nvec, c->sc);
 }
 
-// ---- the diagonal preconditioner (bicg_precond_diagonal / _device)
-// d_dev: the caller's d on the device, caller's numbering. One launch writes 1 / d -- through the permutation on a reordered context
-// -- into the context's ax vector and raises the flag for a zero or non-finite entry; only a clean result is copied into dinv, so a
-// refused call leaves what was installed. ax is free between any two calls: every solver writes it (a product's output) before it
-// reads it, and no product takes it as input, so its halo tail does not matter. Synchronised on return.
-// A captured iteration of method 4 (BICG_GRAPH=1, graph_iteration) holds dinv's ADDRESS as an argument of FDiagQ / FDiagP -- the one
-// pointer of a captured iteration that does not live as long as the context. Whenever the array is freed or a new one is made the
-// captured iteration goes too (and its two eager warm-up iterations are due again); an install into the existing array keeps it.
-static void precond_graph_drop(bicg_ctx *c, int method = BICG_BICGSTAB_DIAG)
-{
-    hipGraphExec_t &g = c->graph_exec[method];
-    if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-    c->graph_warm[method] = 0;
-}
-// one preconditioner per context: whichever kind is held goes, with the captured iteration that holds its address
-static void precond_release(bicg_ctx *c, bool diagonal, bool block)
-{
-    if (diagonal && c->dinv) { precond_graph_drop(c); c->own.free(c->dinv); c->dinv = nullptr; }
-    if (block && c->bjac) {
-        precond_graph_drop(c, BICG_BICGSTAB_BLOCK);
-        c->own.free(c->bjac);
-        c->bjac = nullptr; c->bjac_bs = 0; c->bjac_stride = 0;
-    }
-}
-static double *precond_array(bicg_ctx *c)
-{
-    precond_release(c, false, true);
-    if (!c->dinv) { precond_graph_drop(c); c->dinv = c->own.alloc<double>(c->n_loc); }
-    return c->dinv;
-}
-
-static int precond_install(bicg_ctx *c, const double *d_dev)
-{
-    int flag = 0;
-    launch_dinv(d_dev, c->reordered ? c->ro_perm : nullptr, c->n_loc, c->v.ax, c->refresh_flag, c->sc);
-    BICG_HIP(hipGetLastError());
-    BICG_HIP(hipMemcpyAsync(&flag, c->refresh_flag, sizeof(int), hipMemcpyDeviceToHost, c->sc));
-    BICG_HIP(hipStreamSynchronize(c->sc));
-    if (flag != 0) {                                                   // (zero again for the next call)
-        BICG_HIP(hipMemsetAsync(c->refresh_flag, 0, sizeof(int), c->sc));
-        BICG_HIP(hipStreamSynchronize(c->sc));
-        return 1;
-    }
-    BICG_HIP(hipMemcpyAsync(precond_array(c), c->v.ax, sizeof(double) * c->n_loc, hipMemcpyDeviceToDevice, c->sc));
-    BICG_HIP(hipStreamSynchronize(c->sc));
-    return 0;
-}
-// a rank without rows: its phantom row [1.0] is its own preconditioner
-static int precond_phantom(bicg_ctx *c)
-{
-    const double one = 1.0;
-    BICG_HIP(hipStreamSynchronize(c->sc));
-    BICG_HIP(hipMemcpy(precond_array(c), &one, sizeof one, hipMemcpyHostToDevice));
-    return 0;
-}
-
-// ---- the block-Jacobi preconditioner (bicg_precond_block_diagonal / _device)
-// The planes of the inverted blocks: bs planes, `stride` doubles apart (whole 256-byte lines), in the context's numbering. An install
-// with the bs of the array that is there writes into it; any other makes a new one, and the captured iteration of method 5, which
-// holds the array's address and its bs, goes with the old one (precond_graph_drop's pattern).
-static double *block_array(bicg_ctx *c, int bs)
-{
-    precond_release(c, true, false);
-    if (c->bjac && c->bjac_bs != bs) precond_release(c, false, true);
-    if (!c->bjac) {
-        precond_graph_drop(c, BICG_BICGSTAB_BLOCK);
-        c->bjac_stride = ((size_t)c->n_loc + 31) / 32 * 32;
-        c->bjac = c->own.alloc<double>(c->bjac_stride * (size_t)bs);
-        c->bjac_bs = bs;
-    }
-    return c->bjac;
-}
-// blocks_dev: the caller's blocks on the device. One launch inverts them into scratch of the call and raises the flag for a block it
-// has to refuse; only a clean result goes into the resident planes (a second launch: the change of layout, through the permutation
-// on a reordered context), so a refused call leaves whatever was installed, of either kind. Synchronised on return.
-static int block_install(bicg_ctx *c, const double *blocks_dev, int bs)
-{
-    int flag = 0;
-    double *work = dev_alloc<double>((size_t)bjac_blocks(c->n_loc, bs) * bs * bs);
-    launch_bjac_invert(blocks_dev, c->n_loc, bs, work, c->refresh_flag, c->sc);
-    BICG_HIP(hipGetLastError());
-    BICG_HIP(hipMemcpyAsync(&flag, c->refresh_flag, sizeof(int), hipMemcpyDeviceToHost, c->sc));
-    BICG_HIP(hipStreamSynchronize(c->sc));
-    if (flag != 0) {                                                   // (zero again for the next call)
-        BICG_HIP(hipMemsetAsync(c->refresh_flag, 0, sizeof(int), c->sc));
-        BICG_HIP(hipStreamSynchronize(c->sc));
-        dev_free(work);
-        return 1;
-    }
-    double *planes = block_array(c, bs);
-    launch_bjac_planes(work, c->reordered ? c->ro_perm : nullptr, c->n_loc, bs, planes, c->bjac_stride, c->sc);
-    BICG_HIP(hipGetLastError());
-    BICG_HIP(hipStreamSynchronize(c->sc));
-    dev_free(work);
-    return 0;
-}
-// a rank without rows: its phantom row [1.0] is its own preconditioner, a 1 x 1 block
-static int block_phantom(bicg_ctx *c)
-{
-    const double one = 1.0;
-    BICG_HIP(hipStreamSynchronize(c->sc));
-    BICG_HIP(hipMemcpy(block_array(c, 1), &one, sizeof one, hipMemcpyHostToDevice));
-    return 0;
-}
-// A preconditioned method on a context that does not hold ITS preconditioner: the solving calls return -2 and touch nothing
-static bool diag_refused(const bicg_ctx *c, int method)
-{
-    return c && ((method == BICG_BICGSTAB_DIAG && !c->dinv) || (method == BICG_BICGSTAB_BLOCK && !c->bjac));
-}
-
 extern "C" {
-
-int bicg_precond_diagonal(bicg_ctx *c, const double *d_loc)
-{
-    if (!c) return -1;
-    use_device(c);
-    if (c->phantom) return precond_phantom(c);
-    if (!d_loc) return -1;
-    double *stage = dev_alloc<double>(c->n_loc);                       // a temporary of the call, as bicg_update_values' staging
-    BICG_HIP(hipMemcpyAsync(stage, d_loc, sizeof(double) * c->n_loc, hipMemcpyHostToDevice, c->sc));
-    const int rc = precond_install(c, stage);
-    dev_free(stage);
-    return rc;
-}
-
-int bicg_precond_diagonal_device(bicg_ctx *c, const double *d_d, void *stream)
-{
-    if (!c) return -1;
-    use_device(c);
-    if (c->phantom) return precond_phantom(c);
-    if (!d_d) return -1;
-    cross_begin(c, (hipStream_t)stream);      // what the caller enqueued on its stream (the kernel that fills d_d) comes first
-    return precond_install(c, d_d);
-}
-
-int bicg_precond_block_diagonal(bicg_ctx *c, const double *blocks, int bs)
-{
-    if (!c) return -1;
-    if (bs < 1 || bs > 16) return -2;
-    use_device(c);
-    if (c->phantom) return block_phantom(c);
-    if (!blocks) return -1;
-    const size_t len = (size_t)bjac_blocks(c->n_loc, bs) * bs * bs;
-    double *stage = dev_alloc<double>(len);                            // a temporary of the call, as the elimination's scratch
-    BICG_HIP(hipMemcpyAsync(stage, blocks, sizeof(double) * len, hipMemcpyHostToDevice, c->sc));
-    const int rc = block_install(c, stage, bs);
-    dev_free(stage);
-    return rc;
-}
-
-int bicg_precond_block_diagonal_device(bicg_ctx *c, const double *blocks_d, int bs, void *stream)
-{
-    if (!c) return -1;
-    if (bs < 1 || bs > 16) return -2;
-    use_device(c);
-    if (c->phantom) return block_phantom(c);
-    if (!blocks_d) return -1;
-    cross_begin(c, (hipStream_t)stream);      // what the caller enqueued on its stream (the kernel that fills blocks_d) comes first
-    return block_install(c, blocks_d, bs);
-}
-
-int bicg_precond_clear(bicg_ctx *c)
-{
-    if (!c) return -1;
-    if (!c->dinv && !c->bjac) return 0;
-    use_device(c);
-    BICG_HIP(hipStreamSynchronize(c->sc));
-    precond_release(c, true, true);
-    return 0;
-}
-
-int bicg_precond_kind(bicg_ctx *c) { return !c ? 0 : c->dinv ? 1 : c->bjac ? 2 : 0; }
-
-int bicg_precond_apply(bicg_ctx *c, const double *v_loc, double *z_loc)
-{
-    if (!c || (!c->dinv && !c->bjac)) return -2;
-    use_device(c);
-    v_loc = host_in(c, v_loc); z_loc = host_out(c, z_loc);
-    vec_upload(c, c->v.p, c->stride, v_loc, 1, true);
-    // (the diagonal is the one-plane case in the context's own numbering: z_i = dinv_i v_i, the product FDiagQ / FDiagP form)
-    if (c->dinv) launch_bjac_apply(c->dinv, c->n_loc, 1, nullptr, nullptr, c->v.p, c->v.z, c->n_loc, c->sc);
-    else launch_bjac_apply(c->bjac, c->bjac_stride, c->bjac_bs, c->reordered ? c->ro_perm : nullptr, c->reordered ? c->ro_inv : nullptr,
-                           c->v.p, c->v.z, c->n_loc, c->sc);
-    BICG_HIP(hipGetLastError());
-    vec_download(c, z_loc, c->v.z, c->stride, 1, true);
-    BICG_HIP(hipStreamSynchronize(c->sc));
-    return 0;
-}
-
-int bicg_csr_block_diagonal(const CSR_Matrix *diag, int bs, double *blocks_out)
-{
-    if (bs < 1 || bs > 16) return -2;      // (nothing written)
-    const size_t nb = ((size_t)diag->rows + (size_t)bs - 1) / (size_t)bs;
-    std::fill(blocks_out, blocks_out + nb * (size_t)bs * (size_t)bs, 0.0);
-    int missing = 0;
-    for (unsigned i = 0; i < diag->rows; ++i) {
-        const unsigned base = i / (unsigned)bs * (unsigned)bs;
-        double *row = blocks_out + (size_t)i * (size_t)bs;             // (block k, row a) starts at (k bs + a) bs = i bs
-        unsigned stored = 0;                                           // the in-block columns met so far, a bit each: the first one assigns
-        bool have = false;
-        for (unsigned k = diag->ptr[i]; k < diag->ptr[i + 1]; ++k) {
-            const unsigned col = diag->col[k];
-            if (col < base || col - base >= (unsigned)bs) continue;
-            const unsigned j = col - base;
-            row[j] = (stored >> j & 1u) ? row[j] + diag->val[k] : diag->val[k];
-            stored |= 1u << j;
-            if (col == i) have = true;
-        }
-        if (!have) ++missing;
-    }
-    return missing;
-}
-
-int bicg_csr_diagonal(const CSR_Matrix *diag, double *d_out)
-{
-    int missing = 0;
-    for (unsigned i = 0; i < diag->rows; ++i) {
-        bool have = false;
-        double sum = 0.0;
-        for (unsigned k = diag->ptr[i]; k < diag->ptr[i + 1]; ++k)
-            if (diag->col[k] == i) { sum = have ? sum + diag->val[k] : diag->val[k]; have = true; }
-        d_out[i] = have ? sum : 0.0;
-        if (!have) ++missing;
-    }
-    return missing;
-}
 
 int bicg_load_device(bicg_ctx *c, const double *x0_d, const double *b_d, void *stream)
 {
@@ -562,32 +337,6 @@ int bicg_spmv_bench(bicg_ctx *c, int reps, double *ms_per_spmv)
     (void)hipEventDestroy(a); (void)hipEventDestroy(b);
     if (c->p2p) fetch_scal(c);
     *ms_per_spmv = (double)ms / (reps > 0 ? reps : 1);
-    return 0;
-}
-
-int bicg_precond_apply_bench(bicg_ctx *c, int reps, double *ms_per_apply)
-{
-    if (!c || (!c->dinv && !c->bjac)) return -2;
-    use_device(c);
-    std::vector<double> ones(c->n_loc, 1.0);
-    BICG_HIP(hipMemcpyAsync(c->v.p, ones.data(), sizeof(double) * c->n_loc, hipMemcpyHostToDevice, c->sc));
-    BICG_HIP(hipStreamSynchronize(c->sc));
-    auto apply = [&]() {
-        if (c->dinv) launch_bjac_apply(c->dinv, c->n_loc, 1, nullptr, nullptr, c->v.p, c->v.z, c->n_loc, c->sc);
-        else launch_bjac_apply(c->bjac, c->bjac_stride, c->bjac_bs, c->reordered ? c->ro_perm : nullptr, c->reordered ? c->ro_inv : nullptr,
-                               c->v.p, c->v.z, c->n_loc, c->sc);
-    };
-    for (int i = 0; i < 3; ++i) apply();
-    hipEvent_t a, b;
-    BICG_HIP(hipEventCreate(&a)); BICG_HIP(hipEventCreate(&b));
-    BICG_HIP(hipEventRecord(a, c->sc));
-    for (int i = 0; i < reps; ++i) apply();
-    BICG_HIP(hipEventRecord(b, c->sc));
-    BICG_HIP(hipEventSynchronize(b));
-    float ms = 0.f;
-    BICG_HIP(hipEventElapsedTime(&ms, a, b));
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    *ms_per_apply = (double)ms / (reps > 0 ? reps : 1);
     return 0;
 }
 

@@ -177,46 +177,35 @@ bool p2p_fell_back(bicg_ctx *c)
     return true;
 }
 
-// jacobi_bicgstab: diag(A) of the caller's diag block, refused like a matrix that is not square when a row stores none
-std::vector<double> jacobi_diagonal(const CSR_Matrix *diag)
-{
-    std::vector<double> d(std::max<size_t>(diag->rows, 1), 0.0);
-    if (bicg_csr_diagonal(diag, d.data()) != 0) {
-        fprintf(stderr, "Error: matrix has rows without a diagonal entry.\n");
-        exit(1);
+// jacobi_bicgstab / block_jacobi_bicgstab: the preconditioner the method needs (NONE: nothing to do), read from the caller's diag
+// block -- diag(A), or its bs x bs diagonal blocks -- and refused like a matrix that is not square.
+// It is installed on the resident context by EVERY call: whether the context was created, refreshed or reused by this call does not
+// say what it holds -- another drop-in call may have refreshed the values since (BICG_DROPIN_CACHE=2 leaves the preconditioner
+// alone), or the caller may have installed one of its own on bicg_dropin_context. One upload and one or two launches, beside the
+// pass over the whole matrix that dropin_key makes for every call anyway.
+struct DropinPrecond {
+    Precond::Kind kind;
+    int bs;
+    std::vector<double> data;
+    void prepare(const CSR_Matrix *diag)
+    {
+        if (kind == Precond::DIAGONAL) {
+            data.assign(std::max<size_t>(diag->rows, 1), 0.0);
+            if (bicg_csr_diagonal(diag, data.data()) != 0) { fprintf(stderr, "Error: matrix has rows without a diagonal entry.\n"); exit(1); }
+        }
+        if (kind == Precond::BLOCK) {
+            if (bs < 1 || bs > 16) { fprintf(stderr, "Error: block size %d is outside 1..16.\n", bs); exit(1); }
+            data.assign(std::max<size_t>(((size_t)diag->rows + bs - 1) / bs * bs * bs, 1), 0.0);
+            (void)bicg_csr_block_diagonal(diag, bs, data.data());      // (rows without a stored (i,i): a block without one may well be regular)
+        }
     }
-    return d;
-}
-// ... installed on the resident context by EVERY call: whether the context was created, refreshed or reused by this call does not
-// say whose diagonal it holds -- another drop-in call may have refreshed the values since (BICG_DROPIN_CACHE=2 leaves the
-// preconditioner alone), or the caller may have installed a diagonal of its own on bicg_dropin_context. One upload of a vector and
-// one launch, beside the pass over the whole matrix that dropin_key makes for every call anyway.
-void jacobi_install(bicg_ctx *c, const std::vector<double> &d)
-{
-    if (bicg_precond_diagonal(c, c->phantom ? nullptr : d.data()) != 0) {
-        fprintf(stderr, "Error: matrix has a zero or non-finite diagonal entry.\n");
-        exit(1);
+    void install(bicg_ctx *c) const
+    {
+        const double *src = c->phantom ? nullptr : data.data();          // a rank without rows passes null
+        if (kind == Precond::DIAGONAL && bicg_precond_diagonal(c, src) != 0) { fprintf(stderr, "Error: matrix has a zero or non-finite diagonal entry.\n"); exit(1); }
+        if (kind == Precond::BLOCK && bicg_precond_block_diagonal(c, src, bs) != 0) { fprintf(stderr, "Error: matrix has a singular diagonal block.\n"); exit(1); }
     }
-}
-
-// block_jacobi_bicgstab: the bs x bs diagonal blocks of the caller's diag block, installed by every call like jacobi's diagonal
-std::vector<double> jacobi_blocks(const CSR_Matrix *diag, int bs)
-{
-    if (bs < 1 || bs > 16) {
-        fprintf(stderr, "Error: block size %d is outside 1..16.\n", bs);
-        exit(1);
-    }
-    std::vector<double> blk(std::max<size_t>(((size_t)diag->rows + bs - 1) / bs * bs * bs, 1), 0.0);
-    (void)bicg_csr_block_diagonal(diag, bs, blk.data());      // (rows without a stored (i,i): a block without one may well be regular)
-    return blk;
-}
-void block_jacobi_install(bicg_ctx *c, const std::vector<double> &blk, int bs)
-{
-    if (bicg_precond_block_diagonal(c, c->phantom ? nullptr : blk.data(), bs) != 0) {
-        fprintf(stderr, "Error: matrix has a singular diagonal block.\n");
-        exit(1);
-    }
-}
+};
 
 int dropin(int method, CSR_Matrix *diag, CSR_Matrix *offd, INFO_Matrix *info, double *x, double *r, int krr, int nrr, int bs = 0)
 {
@@ -224,15 +213,11 @@ int dropin(int method, CSR_Matrix *diag, CSR_Matrix *offd, INFO_Matrix *info, do
     bicg_options o;
     env_options(&o);
     o.krr = krr; o.nrr = nrr;
-    const bool jacobi = method == BICG_BICGSTAB_DIAG;
-    std::vector<double> dj;
-    const bool block = method == BICG_BICGSTAB_BLOCK;
-    if (jacobi) dj = jacobi_diagonal(diag);
-    if (block) dj = jacobi_blocks(diag, bs);
+    DropinPrecond pc{precond_kind_of(method), bs, {}};
+    pc.prepare(diag);
     bicg_ctx *c = dropin_context(diag, offd, info);
     if (!c) die("bicg_create", "failed");
-    if (jacobi) jacobi_install(c, dj);
-    if (block) block_jacobi_install(c, dj, bs);
+    pc.install(c);
     bicg_result res;
     // The peer-to-peer data path is chosen automatically when its self-test passes (bicg_comm_init_mpi "auto"). Should it
     // fail in a real solve all the same -- a wait for a peer times out -- the solve is repeated on the transport's own
@@ -245,8 +230,7 @@ int dropin(int method, CSR_Matrix *diag, CSR_Matrix *offd, INFO_Matrix *info, do
         memcpy(r, b.data(), sizeof(double) * b.size());
         c = dropin_context(diag, offd, info);
         if (!c) die("bicg_create", "failed");
-        if (jacobi) jacobi_install(c, dj);
-        if (block) block_jacobi_install(c, dj, bs);
+        pc.install(c);
         k = bicg_solve(c, method, x, r, &o, &res);
     }
     dropin_release(c);

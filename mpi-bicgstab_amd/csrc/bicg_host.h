@@ -7,6 +7,7 @@
 //                     host only: bicg_plan.h) into bicg_ctx::sell / diag / offd, slice descriptors, stencil plan, transport,
 //                     persistent set-up, destroy (clears the context's DevOwner: the one owner of its device memory)
 //   bicg_refresh.cpp  bicg_update_values / bicg_update_values_device: new values for the resident matrix, written in place
+//   bicg_precond.cpp  the context's preconditioner (struct Precond): install, release, apply, bicg_precond_* / bicg_csr_*diagonal
 //   bicg_dropin.cpp   the reference's own symbols (solver.h, shifted_solver.h, shifted_switching_solver.h), matrix residency
 //   bicg_api.cpp      the additive handle API (load / fetch / spmv / dot / spmm / info calls; their *_device variants)
 #pragma once
@@ -105,6 +106,36 @@ struct DevOwner {
     }
 };
 
+// The preconditioner a context holds (bicg_precond.cpp; DESIGN.md sections 4.20, 4.21): at most one, of one kind. `planes` is in the
+// context's numbering, allocated through bicg_ctx::own by the first install of its kind and block size, freed by an install of the
+// other kind or another bs, by bicg_precond_clear and by bicg_destroy. NONE: planes null, bs and stride 0.
+struct Precond {
+    enum Kind { NONE = 0, DIAGONAL = 1, BLOCK = 2 };   // the values bicg_precond_kind returns
+    Kind   kind   = NONE;
+    double *planes = nullptr;   // DIAGONAL: 1 / d, one plane; BLOCK: bs planes of the inverted blocks (csrc/bicg_bjacobi.hip)
+    int    bs     = 0;          // DIAGONAL: 1
+    size_t stride = 0;          // doubles between planes. DIAGONAL: n_loc; BLOCK: n_loc rounded up to 32 (whole 256-byte lines)
+};
+
+// What the host code needs to know about a solver method (the enum of include/bicgstab_hip.h), in one place
+struct MethodInfo {
+    int nvec;                   // work vectors counted for the matrix-stream policy (run_begin)
+    bool pipelined;             // dot groups deferred across a product: consumer-side finish (bicg_ctx::wave_mode)
+    Precond::Kind precond;      // the preconditioner the method needs on the context
+    bool persist;               // may take the persistent launch at all (run_iterate decides per context)
+};
+constexpr MethodInfo kMethod[] = {
+    {6, false, Precond::NONE, true},         // BICG_BICGSTAB
+    {8, false, Precond::NONE, true},         // BICG_CA_BICGSTAB
+    {10, true, Precond::NONE, true},         // BICG_PIPE_BICGSTAB
+    {11, true, Precond::NONE, true},         // BICG_PIPE_BICGSTAB_RR
+    {9, false, Precond::DIAGONAL, false},    // BICG_BICGSTAB_DIAG: the plain one's six, two hat vectors, 1 / d
+    {8, false, Precond::BLOCK, false},       // BICG_BICGSTAB_BLOCK: ... and the bs planes, which run_begin adds
+};
+constexpr int kMethods = (int)(sizeof kMethod / sizeof kMethod[0]);
+static_assert(BICG_BICGSTAB == 0 && BICG_BICGSTAB_BLOCK == kMethods - 1, "kMethod follows the method enum");
+inline Precond::Kind precond_kind_of(int method) { return method >= 0 && method < kMethods ? kMethod[method].precond : Precond::NONE; }
+
 constexpr unsigned kWaitCap = 4096;      // samples per row of PersistArgs::waitlog
 struct bicg_ctx {
     Comm *comm = nullptr;                  // null once the communicator has been replaced (contexts_orphan)
@@ -187,15 +218,7 @@ struct bicg_ctx {
     bool inline_apply = true;       // BICG_P2P_INLINE_APPLY=0: always use the separate apply kernel
     int fault_after = 0;            // BICG_TEST="p2p-fault-after=n" (tests): from the n-th exchange on this rank sends nothing
 
-    // diagonal preconditioner (bicg_precond_diagonal; BICG_BICGSTAB_DIAG): 1 / d, n_loc doubles in the
-    // context's numbering; null: none installed. Allocated by the first install, freed by bicg_precond_clear / bicg_destroy
-    double *dinv = nullptr;
-    // block-Jacobi preconditioner (bicg_precond_block_diagonal; BICG_BICGSTAB_BLOCK): the inverted bs x bs
-    // blocks as bjac_bs planes of bjac_stride doubles in the context's numbering (csrc/bicg_bjacobi.hip); null: none installed. At most
-    // one of dinv / bjac is held: a successful install of one kind releases the other
-    double *bjac = nullptr;
-    int bjac_bs = 0;
-    size_t bjac_stride = 0;
+    Precond pc;                     // the one preconditioner of the context (bicg_precond.cpp)
 
     // vectors and scalars
     double *slab = nullptr;
@@ -362,9 +385,9 @@ struct bicg_ctx {
 
     // hipGraph replay of the iteration body (BICG_GRAPH): one captured iteration per method
     int graph_mode = -1;                 // -1 auto, 0 off, 1 on
-    hipGraphExec_t graph_exec[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int graph_warm[6] = {0, 0, 0, 0, 0, 0};    // eager iterations done since the context was created
-    bool graph_nt[6] = {false, false, false, false, false, false};
+    hipGraphExec_t graph_exec[kMethods] = {};
+    int graph_warm[kMethods] = {};       // eager iterations done since the context was created
+    bool graph_nt[kMethods] = {};
     // now_n > 0: the group is closed by group_now(now_n, phase) right after this producer (not
     // deferred); with the peer-to-peer transport the producer's finishing workgroup then collects
     // and applies it in-kernel and group_now launches nothing.
@@ -523,6 +546,10 @@ void sell_order_for_big_grids(bicg_ctx *c, uint32_t ngroups);
 bool persist_chunk(bicg_ctx *c, int niter);
 void persist_account(bicg_ctx *c);
 bool persist_chunk_shifted(bicg_ctx *c, int mode, int niter, int it0, int nsig, int seed, double shift);
+// ---- the context's preconditioner (bicg_precond.cpp)
+void precond_apply(bicg_ctx *c, const double *in, double *out);      // out = M^-1 in, one launch on the compute stream
+// a preconditioned method on a context that does not hold ITS preconditioner: the solving calls return -2 and touch nothing
+inline bool diag_refused(const bicg_ctx *c, int method) { return c && precond_kind_of(method) != Precond::NONE && c->pc.kind != precond_kind_of(method); }
 // ---- drop-in entry points (bicg_dropin.cpp)
 void check_square(const INFO_Matrix *info);
 void env_options(bicg_options *o);

@@ -1,5 +1,6 @@
 // bicg_solver.cpp -- GPU-resident iteration drivers behind include/bicgstab_hip.h (the C ABI itself: bicg_api.cpp, bicg_dropin.cpp;
-// contexts and plans: bicg_create.cpp; the shifted family: bicg_shifted.cpp; what they share: bicg_host.h).
+// contexts and plans: bicg_create.cpp; the shifted family: bicg_shifted.cpp; the preconditioner: bicg_precond.cpp; what they share:
+// bicg_host.h).
 //
 // One context per rank: the rank's diag/offd CSR blocks, the SpMV plan (row blocks, interior /
 // boundary split, halo lists), twelve vectors of rows+halo doubles, and a small device-resident
@@ -630,11 +631,12 @@ bool plain_handover(const bicg_ctx *c)
 struct Driver {
     bicg_ctx *c;
     int method;
+    Precond::Kind hat; // the preconditioner of the plain iteration: how the hat vectors p^ (v.z) and q^ (v.w) are formed, NONE: not at all
     int krr, nrr;
     Vecs &v;
     unsigned vg;       // workgroups of an element-wise kernel
 
-    Driver(bicg_ctx *ctx, int m, int kr, int nr) : c(ctx), method(m), krr(kr), nrr(nr), v(ctx->v), vg(vec_grid(ctx->v.n)) {}
+    Driver(bicg_ctx *ctx, int m, int kr, int nr) : c(ctx), method(m), hat(precond_kind_of(m)), krr(kr), nrr(nr), v(ctx->v), vg(vec_grid(ctx->v.n)) {}
 
     // element-wise kernel without / with dots: it finishes the open group, then opens its own
     template <class Fn> void vec(Fn launch)
@@ -654,25 +656,15 @@ struct Driver {
 
     void init()
     {
-        const bool plain = method == BICG_BICGSTAB;
+        const bool plain = method == BICG_BICGSTAB || hat != Precond::NONE;      // the plain iteration, preconditioned or not
         const bool rr = method == BICG_PIPE_BICGSTAB_RR || (method == BICG_PIPE_BICGSTAB && c->opt.rr_drift > 0.0);
-        if (method == BICG_BICGSTAB_DIAG) {
-            spmv(c, v.x, v.ax, 0, nullptr, c->red(0, PH_NONE));                       // Ax = A x0
-            launch_init_residual_diag(v, c->dinv, here(), c->red(0, PH_INIT, true, 1));   // r, r# = r, p = r, p^ = dinv o p, (r,r)
-            group_now(c, 1, PH_INIT);
-            return;
-        }
-        if (method == BICG_BICGSTAB_BLOCK) {
-            spmv(c, v.x, v.ax, 0, nullptr, c->red(0, PH_NONE));                       // Ax = A x0
-            launch_init_residual(v, true, false, here(), c->red(0, PH_INIT, true, 1));    // r = b - Ax, r# = r, p = r, (r,r)
-            group_now(c, 1, PH_INIT);
-            block_apply(v.p, v.z);                                                    // p^ = M^-1 p
-            return;
-        }
         if (!c->wave_mode) {
             spmv(c, v.x, v.ax, 0, nullptr, c->red(0, PH_NONE));                       // Ax = A x0
-            launch_init_residual(v, plain, rr, here(), c->red(0, PH_INIT, true, 1));  // r = b - Ax, r# = r, (r,r)
+            // r = b - Ax, r# = r, (r,r); the plain iterations: p = r; DIAGONAL: and p^ = dinv o p in the same pass
+            if (hat == Precond::DIAGONAL) launch_init_residual_diag(v, c->pc.planes, here(), c->red(0, PH_INIT, true, 1));
+            else launch_init_residual(v, plain, rr, here(), c->red(0, PH_INIT, true, 1));
             group_now(c, 1, PH_INIT);
+            if (hat == Precond::BLOCK) precond_apply(c, v.p, v.z);                    // p^ = M^-1 p
             if (plain) return;
             spmv(c, v.r, v.w, 1, v.r, c->red(0, PH_INIT_ALPHA, true, 1));             // w = A r, (r,w)
             group_now(c, 1, PH_INIT_ALPHA);
@@ -714,9 +706,16 @@ struct Driver {
         return L;
     }
 
+    // Plain BiCGStab, as it stands or right-preconditioned (`hat`; DESIGN.md sections 4.20, 4.21): one sequence of operations, dot
+    // groups and phases. Preconditioned, the products take the hat vectors p^ = M^-1 p (v.z) and q^ = M^-1 q (v.w) -- idle in the
+    // plain iteration, zeroed with their halo tails by run_begin -- and x is updated with them; r stays the residual of the caller's
+    // system. DIAGONAL forms them in the pass that produces q / p (no launch added). BLOCK cannot: p is updated in place and a row's
+    // block-mates live in other lanes or workgroups, so each takes a launch of k_bjac_apply (seven launches), which writes v.z / v.w
+    // only -- iterations enqueued behind a converged one change neither x, r nor the scalars. Both always run the multi-launch form
+    // with the producer-side finish: the hand-over is the unpreconditioned method's alone.
     void iter_plain()   // reference src/solver.c:88-119
     {
-        if (handover()) {
+        if (hat == Precond::NONE && handover()) {
             spmv(c, v.p, v.s, 1, v.rh, hand_produce(PH_PLAIN_ALPHA, 1));      // s = A p, (r#,s)
             launch_plain_q(v, hand_consume());                                // -> alpha ; q = r - alpha s
             spmv(c, v.r, v.y, 2, v.r, hand_produce(PH_OMEGA, 2));             // y = A q, (q,y), (y,y)
@@ -727,54 +726,21 @@ struct Driver {
             launch_plain_p(v, hand_consume());                                // -> beta, k++ ; p = r + beta (p - omega s)
             return;
         }
-        spmv(c, v.p, v.s, 1, v.rh, c->red(0, PH_PLAIN_ALPHA, true, 1));   // s = A p, (r#,s) -> alpha
+        const double *dinv = c->pc.planes;
+        spmv(c, hat ? v.z : v.p, v.s, 1, v.rh, c->red(0, PH_PLAIN_ALPHA, true, 1));   // s = A p (A p^), (r#,s) -> alpha
         group_now(c, 1, PH_PLAIN_ALPHA);
-        launch_plain_q(v, here());                              // q = r - alpha s
-        spmv(c, v.r, v.y, 2, v.r, c->red(0, PH_OMEGA, true, 2));          // y = A q, (q,y), (y,y) -> omega
+        if (hat == Precond::DIAGONAL) launch_diag_q(v, dinv, here());   // q = r - alpha s (in v.r) ; q^ = dinv o q
+        else launch_plain_q(v, here());
+        if (hat == Precond::BLOCK) precond_apply(c, v.r, v.w);          // q^ = M^-1 q
+        spmv(c, hat ? v.w : v.r, v.y, 2, v.r, c->red(0, PH_OMEGA, true, 2));          // y = A q (A q^), (q,y), (y,y) -> omega
         group_now(c, 2, PH_OMEGA);
-        launch_plain_xr(v, here(), c->red(0, PH_PLAIN_END, true, 2));    // x, r, (r,r), (r#,r) -> beta, k++
+        // x += alpha p + omega q (alpha p^ + omega q^), r, (r,r), (r#,r) -> beta, k++
+        if (hat) launch_diag_xr(v, here(), c->red(0, PH_PLAIN_END, true, 2));
+        else launch_plain_xr(v, here(), c->red(0, PH_PLAIN_END, true, 2));
         group_now(c, 2, PH_PLAIN_END);
-        launch_plain_p(v, here());                              // p = r + beta (p - omega s)
-    }
-
-    // Right-preconditioned with M = diag(d): iter_plain's operations in its order, the products take the
-    // hat vectors p^ = dinv o p (v.z) and q^ = dinv o q (v.w) -- idle in the plain iteration, zeroed with their halo tails by
-    // run_begin -- and x is updated with them; r stays the residual of the caller's system. Same dot groups and phases, no launch
-    // added; always the multi-launch form with the producer-side finish (no hand-over, no persistent launch).
-    void iter_diag()
-    {
-        spmv(c, v.z, v.s, 1, v.rh, c->red(0, PH_PLAIN_ALPHA, true, 1));   // s = A p^, (r#,s) -> alpha
-        group_now(c, 1, PH_PLAIN_ALPHA);
-        launch_diag_q(v, c->dinv, here());                      // q = r - alpha s ; q^ = dinv o q
-        spmv(c, v.w, v.y, 2, v.r, c->red(0, PH_OMEGA, true, 2));          // y = A q^, (q,y), (y,y) -> omega
-        group_now(c, 2, PH_OMEGA);
-        launch_diag_xr(v, here(), c->red(0, PH_PLAIN_END, true, 2));     // x += alpha p^ + omega q^, r, (r,r), (r#,r) -> beta, k++
-        group_now(c, 2, PH_PLAIN_END);
-        launch_diag_p(v, c->dinv, here());                      // p = r + beta (p - omega s) ; p^ = dinv o p
-    }
-
-    // Right-preconditioned with the block diagonal of bicg_precond_block_diagonal: iter_diag with the fused
-    // hat products replaced by the plain functors plus one launch of k_bjac_apply each -- p is updated in place and a row's
-    // block-mates live in other lanes or workgroups, so the hat vector cannot be formed by the pass that produces p or q. Seven
-    // launches; the apply launches write v.z / v.w only, so iterations enqueued behind a converged one change neither x, r nor
-    // the scalars. Same dot groups and phases, producer-side finish, multi-launch.
-    void block_apply(const double *in, double *out)
-    {
-        launch_bjac_apply(c->bjac, c->bjac_stride, c->bjac_bs, c->reordered ? c->ro_perm : nullptr, c->reordered ? c->ro_inv : nullptr, in, out,
-                          c->n_loc, c->sc);
-    }
-    void iter_block()
-    {
-        spmv(c, v.z, v.s, 1, v.rh, c->red(0, PH_PLAIN_ALPHA, true, 1));   // s = A p^, (r#,s) -> alpha
-        group_now(c, 1, PH_PLAIN_ALPHA);
-        launch_plain_q(v, here());                              // q = r - alpha s (in v.r)
-        block_apply(v.r, v.w);                                  // q^ = M^-1 q
-        spmv(c, v.w, v.y, 2, v.r, c->red(0, PH_OMEGA, true, 2));          // y = A q^, (q,y), (y,y) -> omega
-        group_now(c, 2, PH_OMEGA);
-        launch_diag_xr(v, here(), c->red(0, PH_PLAIN_END, true, 2));     // x += alpha p^ + omega q^, r, (r,r), (r#,r) -> beta, k++
-        group_now(c, 2, PH_PLAIN_END);
-        launch_plain_p(v, here());                              // p = r + beta (p - omega s)
-        block_apply(v.p, v.z);                                  // p^ = M^-1 p
+        if (hat == Precond::DIAGONAL) launch_diag_p(v, dinv, here());   // p = r + beta (p - omega s) ; p^ = dinv o p
+        else launch_plain_p(v, here());
+        if (hat == Precond::BLOCK) precond_apply(c, v.p, v.z);          // p^ = M^-1 p
     }
 
     void iter_ca()      // reference src/solver.c:217-251
@@ -850,10 +816,8 @@ struct Driver {
     void iterate(int it, bool force_replace = false, bool last = true)
     {
         switch (method) {
-        case BICG_BICGSTAB: iter_plain(); break;
+        case BICG_BICGSTAB: case BICG_BICGSTAB_DIAG: case BICG_BICGSTAB_BLOCK: iter_plain(); break;
         case BICG_CA_BICGSTAB: iter_ca(); break;
-        case BICG_BICGSTAB_DIAG: iter_diag(); break;
-        case BICG_BICGSTAB_BLOCK: iter_block(); break;
         default: iter_pipe(it, force_replace, last); break;
         }
     }
@@ -916,9 +880,10 @@ void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in)
 {
     bicg_options &o = c->opt;
     if (opt_in) o = *opt_in; else bicg_default_options(&o);
-    if (method < BICG_BICGSTAB || method > BICG_BICGSTAB_BLOCK) die("bicg_run", "unknown method");
-    if (method == BICG_BICGSTAB_DIAG && !c->dinv) die("bicg_run", "BICG_BICGSTAB_DIAG without a preconditioner (bicg_precond_diagonal)");
-    if (method == BICG_BICGSTAB_BLOCK && !c->bjac) die("bicg_run", "BICG_BICGSTAB_BLOCK without a preconditioner (bicg_precond_block_diagonal)");
+    if (method < 0 || method >= kMethods) die("bicg_run", "unknown method");
+    if (diag_refused(c, method))
+        die("bicg_run", precond_kind_of(method) == Precond::DIAGONAL ? "BICG_BICGSTAB_DIAG without a preconditioner (bicg_precond_diagonal)"
+                                                                     : "BICG_BICGSTAB_BLOCK without a preconditioner (bicg_precond_block_diagonal)");
     if (o.max_iter < 0) o.max_iter = 0;
     if (o.check_every < 1) o.check_every = 1;
     c->method = method;
@@ -927,7 +892,7 @@ void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in)
     // chain at the end of the producer (memory system draining) is then the shortest path. The
     // pipelined solvers defer their groups across an SpMV (src/solver.c:363-367, 377-385): there the sums
     // are staged by that SpMV and finished by the kernel that consumes them, off the critical path.
-    c->wave_mode = method == BICG_PIPE_BICGSTAB || method == BICG_PIPE_BICGSTAB_RR;
+    c->wave_mode = kMethod[method].pipelined;
     c->grp = bicg_ctx::Group{};
     c->f1_done = false;
     c->spmv_dir = 0;             // every solve starts in the same direction (its first product toggles this to 1 = reversed):
@@ -938,9 +903,8 @@ void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in)
     // per iteration). Beyond that the matrix only evicts the vectors and is streamed with
     // non-temporal loads instead (Transport, pipelined, 10 vectors: 167.3 vs 173.8 us).
     {
-        // (the preconditioned iterations: the plain one's six, two hat vectors, dinv -- or, block Jacobi, the bs planes added below)
-        static const int nvec[6] = {6, 8, 10, 11, 9, 8};
-        const double ws = (double)c->matrix_bytes + 8.0 * c->stride * (nvec[method] + (method == BICG_BICGSTAB_BLOCK ? c->bjac_bs : 0));
+        // (kMethod counts the vectors; the planes of a block preconditioner come on top, a diagonal is already counted)
+        const double ws = (double)c->matrix_bytes + 8.0 * c->stride * (kMethod[method].nvec + (kMethod[method].precond == Precond::BLOCK ? c->pc.bs : 0));
         // (round 4: with the products alternating direction, ordinary loads pay up to 35 % over the cache -- CA-BiCGStab
         // 166.9 -> 150.6 us per iteration; the pipelined solvers' ten vectors are past that: 157.2 vs 160.9)
         // (round 5, the products of rounds 4-5 and an irregular matrix: ordinary loads win far beyond that -- FEM-like, 1.6 M rows,
@@ -1040,7 +1004,7 @@ bool persist_chunk(bicg_ctx *c, int niter)
     if (c->grp.active) die("internal", "persistent chunk with an open dot group");
     if (c->f1_done) die("internal", "persistent chunk after phase 1 of the next iteration has run");
     const bool plain = c->method == BICG_BICGSTAB;
-    const bool pipe = c->method >= BICG_PIPE_BICGSTAB;
+    const bool pipe = kMethod[c->method].pipelined;
     const unsigned groups = plain ? 3u : 2u;                  // dot groups (tags, mailbox numbers) per iteration
     PersistArgs a = c->persist;
     a.v = c->v; a.S = c->S; a.alarm = c->alarm; a.niter = niter;
@@ -1134,10 +1098,10 @@ int run_iterate(bicg_ctx *c, int nsteps)
     const int stop = std::min(o.max_iter, c->it + std::max(nsteps, 0));
     while (!c->hS->done && c->it < stop) {
         // (section marks are host-side events between launches: the multi-launch forms are what they can time)
-        bool persist = c->method != BICG_BICGSTAB_DIAG && c->method != BICG_BICGSTAB_BLOCK && c->persist_on && !c->time_kernels && !c->time_sections && !c->sec_exhausted &&
-                             ((c->method >= BICG_PIPE_BICGSTAB && (c->persist.rpt == 1u || (c->method == BICG_PIPE_BICGSTAB && o.rr_drift <= 0.0))) ||
-                              ((c->method == BICG_BICGSTAB || c->method == BICG_CA_BICGSTAB) && c->persist_plain && c->persist.rpt == 1u) ||
-                              ((c->method == BICG_BICGSTAB || c->method == BICG_CA_BICGSTAB) && c->persist_plain && c->persist.rpt == 2u && !c->persist.mat_entries));
+        const bool pipe = kMethod[c->method].pipelined;
+        bool persist = kMethod[c->method].persist && c->persist_on && !c->time_kernels && !c->time_sections && !c->sec_exhausted &&
+                             ((pipe && (c->persist.rpt == 1u || (c->method == BICG_PIPE_BICGSTAB && o.rr_drift <= 0.0))) ||
+                              (!pipe && c->persist_plain && (c->persist.rpt == 1u || (c->persist.rpt == 2u && !c->persist.mat_entries))));
         // A persistent launch costs ~27 us of set-up (matrix slices and x window into LDS) and stops by itself at
         // convergence: it covers at least kPersistChunk iterations whatever the host check interval (200 k-row rank,
         // pipelined: 12.5 us per iteration at 16 per launch, 11.0 at 128, 10.9 at 512 -- tools/persist_chunk_times.py)
@@ -1162,7 +1126,7 @@ int run_iterate(bicg_ctx *c, int nsteps)
         sec_mark(c, SEC_STOP);
         c->t_enq += now_sec() - t_chunk;          // (bicg_run_iterate_timed: host time until the chunk's launches were enqueued)
         fetch_scal(c);
-        if (persist && c->method >= BICG_PIPE_BICGSTAB) persist_account(c);
+        if (persist && pipe) persist_account(c);
         if (talk && o.out_iter > 0) {   // reference src/solver.c:122-126
             const int k = c->hS->k;
             const int upto = (k / o.out_iter) * o.out_iter;

@@ -1,5 +1,5 @@
 """`-m gpu`, one rank: the block-Jacobi preconditioner and BICG_BICGSTAB_BLOCK (bicg_precond_block_diagonal, bicg_precond_apply,
-Driver::iter_block, csrc/bicg_bjacobi.hip) through Context.set_block_diagonal / apply_preconditioner /
+Driver::iter_plain, csrc/bicg_bjacobi.hip) through Context.set_block_diagonal / apply_preconditioner /
 solve("bicgstab_block"). Contexts as in tests/test_precond_gpu.py, whose matrices, bundles and byte comparisons are reused: always
 under switches(persist=0).
 
@@ -406,6 +406,52 @@ def test_refused_blocks_leave_what_was_installed_and_installs_allocate_once(coup
     assert H.device_allocations() == before + 1
     assert state(ctx, ctx.solve("bicgstab_block", b, x0=x0, **REAL)) == want
     assert ctx.clear_preconditioner() == 0 and H.device_allocations() == before
+
+
+def test_one_context_holds_one_preconditioner_through_a_sequence_of_installs():
+    """diagonal, block (bs = 4), block (bs = 2), diagonal, clear on ONE context (4099 rows: a partial last block for both widths).
+    After every install the context names the kind just installed, its method solves bit for bit as on a fresh context that holds
+    nothing else, and the other kind's method is refused without touching x and r. A refused install (a singular block while the
+    diagonal is held) changes nothing, and the final clear gives back the one array that was ever held at a time."""
+    A = synth.block_coupled(4099, 4, synth.fem_like, scale_decades=2.0)
+    n = A.rows
+    b, x0 = A.matvec(np.ones(n)), 0.01 * synth._uniform(np.arange(n, dtype=np.int64), 3)
+    opts = dict(tol=0.0, max_iter=8, record_trace=1)
+    d, missing = H.csr_diagonal(A)
+    assert missing == 0
+    install = {"diagonal": lambda c: c.set_diagonal(d),
+               "block4": lambda c: c.set_block_diagonal(H.csr_block_diagonal(A, 4)[0], 4),
+               "block2": lambda c: c.set_block_diagonal(H.csr_block_diagonal(A, 2)[0], 2)}
+    method = {"diagonal": "bicgstab_diag", "block4": "bicgstab_block", "block2": "bicgstab_block"}
+    want = {}
+    for key in install:                                              # once each: a fresh context that holds only this one
+        fresh = context(A)
+        try:
+            assert install[key](fresh) == 0
+            want[key] = state(fresh, fresh.solve(method[key], b, x0=x0, **opts))
+        finally:
+            fresh.close()
+    assert len(set(want.values())) == 3
+    singular = np.array(H.csr_block_diagonal(A, 4)[0]); singular[n // 8, 2, :] = 0.0
+    ctx = context(A)
+    try:
+        ctx.solve("bicgstab", b, x0=x0, **opts)                      # (the trace buffer grows with the first solve)
+        before = H.device_allocations()
+        for step, key in enumerate(("diagonal", "block4", "block2", "diagonal")):
+            assert install[key](ctx) == 0
+            assert ctx.preconditioner() == ("diagonal" if key == "diagonal" else "block_diagonal")
+            assert H.device_allocations() == before + 1
+            if step == 3:                                            # refused: the diagonal stays and answers as before
+                assert ctx.set_block_diagonal(singular, 4) == 1 and ctx.preconditioner() == "diagonal"
+                assert H.device_allocations() == before + 1
+            assert state(ctx, ctx.solve(method[key], b, x0=x0, **opts)) == want[key]
+            other = "bicgstab_block" if key == "diagonal" else "bicgstab_diag"
+            got = ctx.solve(other, b, x0=x0, **opts)
+            assert got["k"] == -2 and got["x"].tobytes() == x0.tobytes() and got["r"].tobytes() == b.tobytes()
+        assert ctx.clear_preconditioner() == 0 and ctx.preconditioner() is None
+        assert H.device_allocations() == before
+    finally:
+        ctx.close()
 
 
 def test_update_values_then_install_equals_a_fresh_context():

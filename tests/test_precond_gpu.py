@@ -1,4 +1,4 @@
-"""`-m gpu`, one rank: the diagonal preconditioner and BICG_BICGSTAB_DIAG (bicg_precond_diagonal, Driver::iter_diag, the FDiag*
+"""`-m gpu`, one rank: the diagonal preconditioner and BICG_BICGSTAB_DIAG (bicg_precond_diagonal, Driver::iter_plain, the FDiag*
 functors of csrc/bicg_vec.hip, csrc/bicg_precond.hip) through Context.set_diagonal / solve("bicgstab_diag").
 
 The exact comparisons rest on two facts: multiplying by 1.0 or by a power of two is exact, and the element-wise dots depend on n
