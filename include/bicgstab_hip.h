@@ -680,6 +680,25 @@ int bicg_persist_plan_sources(const CSR_Matrix *diag, const CSR_Matrix *offd_ren
  *   digest of no bytes). Returns 0 on success. */
 int bicg_sell_plan_digest(const CSR_Matrix *diag, const CSR_Matrix *offd_renumbered, int nranks, unsigned int rows_global,
                           unsigned long long nnz_diag_global, unsigned long long summary[22], unsigned long long digest[26]);
+/* The launch plan of one distributed product y = A x (host only, what every product of every solver asks
+ * before it enqueues anything): which launches the product consists of and how their workgroups share the dot group's partial
+ * slots, as numbers a test can pin. Needs no context and no device; reads no environment.
+ * shape = {0 interior sliced-ELL groups, 1 halo-touching groups, 2 interior CSR row blocks, 3 halo-touching row blocks, 4 row
+ *   blocks in all, 5 every group on the sliced-ELL path, 6 transport (0 one rank, 1 peer-to-peer, 2 hosted), 7 the exchange can
+ *   ride inside the sliced-ELL launch, 8 this rank sends halo values, 9 the hosted exchange runs on its own stream, 10 the
+ *   plane-marching product is available, 11 its workgroups, 12 groups per workgroup, 13 ... of a product with dots, 14 workgroup
+ *   cap of ranks sharing a GPU (0: none)}.
+ * call = {0 fused dots, 1 epilogue (0 none, 1 / 2 pipelined phases, 3 CA-BiCGStab's q / y), 2 shifted product, 3 the dot group
+ *   carries a tail tag, 4 it is a per-wavefront group}.
+ * plan = {0 error (0 none, 1 epilogue 3 without the plane-marching product on one rank, 2 epilogue on a product of several
+ *   launches, 3 the plane-marching launch would decline), 1 groups per workgroup, 2 plane-marching, 3 exchange inside the launch,
+ *   4 one launch over all groups, 5 partial slots the group expects, 6 shard totals of a hand-over group, 7 the group's partial
+ *   count is set from 5, 8 the tail finish stays, 9 steps}; with an error, entries from 5 on say nothing.
+ * steps = 4 rows of {0 kernel family (0 sliced-ELL, 1 sliced-ELL with epilogue, 2 plane-marching, 3 CSR row blocks), 1 list
+ *   (0 all groups, 1 interior groups, 2 halo-touching groups, 3 the fused list, 4 interior row blocks, 5 halo-touching row
+ *   blocks), 2 entries of the list, 3 reads the offd block, 4 exchange inside, 5 first partial slot, 6 runs after the halo has
+ *   landed}, in launch order; rows from plan[9] on are zero. Returns 0, 1 for a null array or an unknown transport. */
+int bicg_spmv_launch_plan(const unsigned int shape[15], const int call[5], unsigned int plan[10], unsigned int steps[28]);
 
 /* Bandwidth-reducing renumbering of a diag block (host only, what bicg_create does under
  * BICG_PLAN="reorder=1|2"). Reverse Cuthill-McKee on the symmetrised pattern (entry (i, j) makes i and j neighbours whichever of

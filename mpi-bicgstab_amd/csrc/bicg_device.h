@@ -541,7 +541,7 @@ extern unsigned g_product_kernels;
 // Both return false when there was nothing to launch. e0/e1 (optional): start/stop events bound to
 // this one kernel (hipExtLaunchKernelGGL) -- the per-kernel durations bench.py's roofline uses.
 bool launch_spmv(const SpmvArgs &a, int ndot, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);        // CSR row-block stream
-unsigned spmv_grid(uint32_t nlist);   // workgroups used by the CSR SpMV for nlist row blocks
+unsigned spmv_grid(uint32_t nlist);   // workgroups used by the CSR SpMV for nlist row blocks (defined in bicg_spmv_plan.cpp)
 void preload_csr_kernels();
 // bicg_spmv_sell.hip (the layouts' kernels: bicg_spmv_sell_lay.hip, one translation unit per layout)
 bool launch_spmv_sell(const SpmvArgs &a, int ndot, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
@@ -550,13 +550,13 @@ bool launch_spmv_sell(const SpmvArgs &a, int ndot, bool with_offd, hipStream_t s
 // applied at the epilogue, a.red receives the phase's dot partials
 bool launch_spmv_sell_epi(const SpmvArgs &a, int epi, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
                           bool fused_halo = false);
-unsigned sell_grid(uint32_t ngroups, int per_wg); // workgroups launched for ngroups 256-row groups
+unsigned sell_grid(uint32_t ngroups, int per_wg); // workgroups launched for ngroups 256-row groups (defined in bicg_spmv_plan.cpp)
 // look up one kernel of every translation unit a context with this sliced-ELL plan launches from (loads their code objects now)
 void preload_kernels(const SellDev &d, bool sell);
 // bicg_stencil.hip
 // plane-marching product of a 7-point grid stencil (bicg_stencil.hip; a.sell.st.on). epi = 1: CA-BiCGStab's q = r - alpha s,
 // y = w - alpha z, (q,y), (y,y) (reference src/solver.c:225-232) on the wavefront's own rows behind z = A s (a.epi.r / a.epi.w)
-unsigned stencil_grid(const StencilDev &st);
+unsigned stencil_grid(const StencilDev &st);      // (defined in bicg_spmv_plan.cpp)
 bool launch_spmv_stencil(const SpmvArgs &a, int ndot, int epi, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 void preload_stencil_kernels();
 // bicg_jagw.hip

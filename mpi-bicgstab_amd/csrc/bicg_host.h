@@ -1,6 +1,6 @@
 // bicg_host.h -- what the host-side translation units of the library share: the context of a rank (struct bicg_ctx), the
 // device-memory helpers and their owner (dev_alloc / dev_free, struct DevOwner), section timing, and the prototypes of the functions that cross file boundaries.
-//   bicg_solver.cpp   dot groups, the distributed SpMV, the four iterations of reference src/solver.c, run_begin / iterate / end
+//   bicg_solver.cpp   dot groups, the distributed SpMV (its launch plan: bicg_spmv_plan.cpp, host only), the four iterations of reference src/solver.c, run_begin / iterate / end
 //   bicg_shifted.cpp  the shifted family (src/shifted_solver.c, src/shifted_switching_solver.c) and its section prints
 //   bicg_multi.cpp    bicg_solve_multi: plain BiCGStab on up to kSpmmCols right-hand sides per pass over the matrix
 //   bicg_create.cpp   bicg_create / bicg_create_device_csr: halo plan, upload of the diag block's plan (made by bicg_sell_plan.cpp,

@@ -1,5 +1,6 @@
 // bicg_plan.h -- the plans that are made on the host without a device: the persistent iteration's (persist_plan_host,
-// bicg_plan.cpp), the sliced-ELL plan of the diag block (sell_plan_host, bicg_sell_plan.cpp) and the renumbering of a badly
+// bicg_plan.cpp), the sliced-ELL plan of the diag block (sell_plan_host, bicg_sell_plan.cpp), the launch plan of a product
+// (spmv_plan, bicg_spmv_plan.cpp) and the renumbering of a badly
 // numbered diag block (reorder_rcm / permute_block, bicg_reorder.cpp). Plain data: device vector
 // types appear as element types only, nothing here calls the HIP runtime or reads the environment.
 #pragma once
@@ -106,6 +107,64 @@ bool sell_plan_host(const CSR_Matrix *diag, const uint32_t *optr, const PlanFact
 constexpr int kSellSummaryLen = 22, kSellDigestLen = 26;
 void sell_plan_summary(const SellPlan &plan, unsigned long long summary[kSellSummaryLen]);
 void sell_plan_digest(const SellPlan &plan, unsigned long long digest[kSellDigestLen]);
+
+// The launch plan of one distributed product y = A x (spmv_plan, bicg_spmv_plan.cpp): every decision about
+// the SHAPE of the product -- which launches exist, over which list, where each one's dot partials start, how many partial slots
+// the group expects -- as a pure function of a few integers, so that the CPU suite pins it (tests/test_spmv_plan.py). spmv()
+// (bicg_solver.cpp) only executes it. No HIP call, no environment, no heap, no static state: it runs once per product on ranks
+// that are host-bound at a few microseconds per launch.
+enum SpmvTransport { SPMV_SINGLE = 0, SPMV_P2P = 1, SPMV_HOSTED = 2 };
+struct SpmvShape {      // what a context says about its product (spmv_shape, bicg_solver.cpp) ...
+    uint32_t ng_int = 0, ng_bnd = 0;      // sliced-ELL groups: interior / halo-touching
+    uint32_t n_int = 0, n_bnd = 0;        // CSR row blocks: interior / halo-touching
+    uint32_t nblk = 0;
+    bool glist_all = false;
+    int transport = SPMV_SINGLE;
+    bool ll_fused = false;                // peer-to-peer: the exchange can ride inside the sliced-ELL launch
+    bool has_send = false;                // ... and this rank has values to push (that launch exists even without groups)
+    bool own_stream = false;              // hosted: the exchange runs on the communication stream
+    bool stencil_ok = false;              // stencil_product(c)
+    uint32_t stencil_wgs = 0;             // stencil_grid(c->sell.st)
+    int sell_gpw = 1, sell_gpw_dots = 1;
+    uint32_t wg_cap = 0;
+};
+struct SpmvCall {       // ... and what one call adds
+    int ndot = 0, epi = 0;
+    bool has_shift = false;
+    bool tail = false;                    // the caller's Reduce carries a tail tag
+    bool wave = false;                    // ... is a per-wavefront group (consumer-side finish)
+};
+enum SpmvFamily { FAM_SELL = 0, FAM_SELL_EPI = 1, FAM_STENCIL = 2, FAM_CSR = 3 };
+enum SpmvList { LIST_ALL = 0, LIST_INT = 1, LIST_BND = 2, LIST_FUSED = 3, LIST_BLK_INT = 4, LIST_BLK_BND = 5 };
+enum SpmvPlanError {
+    SPMV_PLAN_OK = 0,
+    SPMV_ERR_EPI3 = 1,                    // CA-BiCGStab's epilogue without the plane-marching product on one rank
+    SPMV_ERR_EPI_MULTI = 2,               // an epilogue on a product of several launches
+    SPMV_ERR_STENCIL_DECLINED = 3,        // the plane-marching launch would decline: its epilogue with a per-wavefront group
+};
+struct SpmvStep {
+    int family = FAM_SELL, list = LIST_ALL;
+    uint32_t nlist = 0;
+    bool with_offd = false, fused_halo = false;
+    uint32_t slot_base = 0;               // first partial slot of the launch's workgroups
+    bool after_halo = false;              // runs behind the point where the halo has landed
+};
+constexpr int kSpmvMaxSteps = 4;
+struct SpmvPlan {
+    int error = SPMV_PLAN_OK;
+    int groups_per_wg = 1;
+    bool stencil = false, fused = false, merged = false;
+    uint32_t expected = 0;                // partial slots of the dot group = workgroups of all launches
+    uint32_t hand_nsh = 0;                // shard totals a hand-over group leaves (bicg_ctx::Hand::nsh)
+    bool sets_nparts = false;             // bicg_ctx::Group::nparts = expected * wavefronts per workgroup
+    bool tail = false;                    // the tail finish stays (else: arrival tickets)
+    int nsteps = 0;
+    SpmvStep step[kSpmvMaxSteps];
+};
+SpmvPlan spmv_plan(const SpmvShape &s, const SpmvCall &k);
+const char *spmv_plan_error(int error);   // the message spmv() ends the program with
+// bicg_spmv_launch_plan (include/bicgstab_hip.h section 5): lengths of its arrays
+constexpr int kSpmvShapeLen = 15, kSpmvCallLen = 5, kSpmvPlanLen = 10, kSpmvStepLen = 7;
 
 // BICG_PLAN="reorder=1|2" (bicg_reorder.cpp; C views: bicg_reorder_plan / bicg_permute_block, include/bicgstab_hip.h section 5).
 // reorder_rcm: perm[new] = old, reverse Cuthill-McKee on the symmetrised pattern, and the eight stats of bicg_reorder_plan.

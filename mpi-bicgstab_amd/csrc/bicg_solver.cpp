@@ -236,10 +236,81 @@ static unsigned p2p_next_exchange(bicg_ctx *c, Scal *S)
 }
 
 // ---------------------------------------------------------------- distributed SpMV
+// What a context tells spmv_plan (bicg_plan.h) about its product: the only place where the product's grids are read.
+static SpmvShape spmv_shape(const bicg_ctx *c)
+{
+    SpmvShape s;
+    s.ng_int = c->ng_int; s.ng_bnd = c->ng_bnd; s.n_int = c->n_int; s.n_bnd = c->n_bnd; s.nblk = c->nblk;
+    s.glist_all = c->glist_all;
+    s.transport = c->single() ? SPMV_SINGLE : c->p2p ? SPMV_P2P : SPMV_HOSTED;
+    s.ll_fused = c->ll_fused; s.has_send = c->nsend > 0;
+    s.own_stream = hosted(c) && c->comm->stream_ordered() && c->overlap;
+    s.stencil_ok = stencil_product(c);
+    s.stencil_wgs = s.stencil_ok ? stencil_grid(c->sell.st) : 0u;
+    s.sell_gpw = c->sell_gpw; s.sell_gpw_dots = c->sell_gpw_dots; s.wg_cap = c->wg_cap;
+    return s;
+}
+
+// One halo exchange in two halves; afterwards xin[rows .. rows + halo) holds the other ranks' values. Whatever is enqueued on the
+// compute stream between the halves runs while the values travel.
+// peer-to-peer (exchange number seq): the send list is stored straight into the landing rings of the ranks that need it (send =
+// false: BICG_TEST="p2p-fault-after=n"), one kernel decodes the ring slot into the halo tail of x.
+// hosted: pack, then the transport's exchange -- in stream order, or (own_stream) on the communication stream behind the pack, and
+// then halo_start returns the event halo_land makes the compute stream wait for.
+static hipEvent_t halo_start(bicg_ctx *c, double *xin, Scal *S, unsigned seq, bool send, bool own_stream)
+{
+    if (c->p2p) {
+        if (send) launch_halo_push(xin, c->send_idx, c->nsend, c->push_dst0, c->push_stride, seq, S, c->sc);
+        return nullptr;
+    }
+    launch_halo_pack(xin, c->send_idx, c->nsend, c->sendbuf, S, c->sc);
+    if (own_stream) {
+        hipEvent_t ep = c->ev_pack[c->i_pack++ % kEvRing];
+        BICG_HIP(hipEventRecord(ep, c->sc));
+        BICG_HIP(hipStreamWaitEvent(c->sm, ep, 0));
+    }
+    ctx_exchange(c, c->sendbuf, c->scnt.data(), c->sdsp.data(), xin + c->n_loc, c->rcnt.data(), c->rdsp.data(), own_stream ? c->sm : c->sc);
+    if (!own_stream) return nullptr;
+    hipEvent_t eh = c->ev_halo[c->i_halo++ % kEvRing];
+    BICG_HIP(hipEventRecord(eh, c->sm));
+    return eh;
+}
+static void halo_land(bicg_ctx *c, double *xin, Scal *S, unsigned seq, hipEvent_t landed)
+{
+    if (c->p2p) launch_halo_unpack(c->halo_ring, c->halo, seq, xin + c->n_loc, S, c->p2p->timeout_ticks, c->sc);
+    else if (landed) BICG_HIP(hipStreamWaitEvent(c->sc, landed, 0));
+}
+
+// one step of the plan through its launch wrapper; false: there was nothing to launch
+static bool launch_step(bicg_ctx *c, SpmvArgs &a, const SpmvStep &t, int ndot, int epi, hipEvent_t e0, hipEvent_t e1)
+{
+    switch (t.list) {
+    case LIST_ALL: a.glist = nullptr; break;
+    case LIST_INT: a.glist = c->glist_int_identity ? nullptr : c->glist_int; break;
+    case LIST_BND: a.glist = c->glist_bnd; break;
+    case LIST_FUSED: a.glist = c->glist_ll; break;
+    case LIST_BLK_INT: a.glist = nullptr; a.desc = c->desc_int; break;      // (the CSR kernels read no group list)
+    case LIST_BLK_BND: a.glist = nullptr; a.desc = c->desc_bnd; break;
+    }
+    a.nlist = t.nlist; a.red.slot_base = t.slot_base;
+    switch (t.family) {
+    case FAM_STENCIL:
+        // (the plan only selects tilings the kernel is built for, and the epilogue only with ticket reductions: a launch that
+        // is declined here would leave y unwritten and a ticket group waiting for partial sums that never come)
+        if (!launch_spmv_stencil(a, ndot, epi == 3 ? 1 : 0, c->sc, e0, e1)) die("internal", spmv_plan_error(SPMV_ERR_STENCIL_DECLINED));
+        return true;
+    case FAM_SELL_EPI: return launch_spmv_sell_epi(a, epi, t.with_offd, c->sc, e0, e1, t.fused_halo);
+    case FAM_CSR: return launch_spmv(a, ndot, t.with_offd, c->sc, e0, e1);
+    default: return launch_spmv_sell(a, ndot, t.with_offd, c->sc, e0, e1, t.fused_halo);
+    }
+}
+
 // y = A x (+ fused dots). Replaces MPI_csr_spmv_ovlap (reference src/matrix.c:428-441): the halo
 // exchange runs on the communication stream while the interior row blocks are multiplied; row
 // blocks that touch the halo run after it has landed. Every row is produced by exactly one
 // workgroup as (0 + sum_diag) + sum_offd, the reference's order.
+// Which launches that takes, over which lists and with which partial slots: spmv_plan (bicg_spmv_plan.cpp). Here the plan is
+// enqueued: start the exchange, the steps that do not read the halo, land it, the steps that do, the joins.
 // fin: a dot group of earlier kernels that the first kernel launched here finishes (grp_for_spmv).
 void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Reduce red, Finish fin, int epi,
           Scal *S)
@@ -258,17 +329,6 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
     Scal *const Sh = a.S;        // every kernel of this call reads the same scalar block
     a.nt = c->sell_nt ? 1 : 0;
     a.shift = c->cur_shift; a.has_shift = c->cur_has_shift ? 1 : 0;
-    // Up to four launches share one dot group (one partial slot per workgroup, numbered in launch
-    // order): {sliced-ELL groups, CSR row blocks} x {interior, halo-touching}.
-    a.groups_per_wg = ndot > 0 ? c->sell_gpw_dots : c->sell_gpw;
-    // Ranks SHARING a GPU (tests; bicg_ctx::wg_cap): a launch with the halo exchange inside may consist of workgroups that ALL wait
-    // for another rank's values (a numbering without locality: every 256-row group touches the halo). The first rank's launch would
-    // fill the device with waiting workgroups and keep the launches that hold the awaited pushes out until the time-out; every
-    // rank's launch, pushing workgroups included, has to fit beside the others'.
-    if (c->wg_cap && c->p2p && c->ll_fused) {
-        const unsigned room = c->wg_cap > 80u ? c->wg_cap - 64u : 16u, ng = c->ng_int + c->ng_bnd;
-        a.groups_per_wg = std::max<int>(a.groups_per_wg, (int)((ng + room - 1) / room));
-    }
     a.xcd_map = c->sell_xcd;
     // Consecutive products of a solve run over the matrix in alternating directions (BICG_SELL_ALT=0: always forward): matrix +
     // vectors of a Transport-sized system exceed the 256 MiB Infinity Cache by a quarter, so a product that starts where the
@@ -276,159 +336,72 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
     // evict it just before it is needed. Rows, hence results of the product, are unaffected; the dot partials of a
     // reversed launch land in mirrored slots (a different, equally fixed association).
     a.reverse = (c->sell_alt && c->single()) ? (c->spmv_dir ^= 1) : 0;
-    // the plane-marching product (bicg_stencil.hip) takes the rank's halo-free planes in one launch of its own tiling; across ranks
-    // the halo-touching planes follow behind the exchange through the slice-by-slice kernel, as separate launches (never the
-    // launch with the exchange inside)
-    const bool stencil = stencil_product(c) && (epi == 0 || epi == 3) && !a.has_shift;
-    if (epi == 3 && !(stencil && c->single())) die("internal", "CA-BiCGStab's fused q / y epilogue without the plane-marching product");
-    const unsigned g_si = stencil ? stencil_grid(c->sell.st) : sell_grid(c->ng_int, a.groups_per_wg), g_ci = spmv_grid(c->n_int);
-    const unsigned g_sb = sell_grid(c->ng_bnd, a.groups_per_wg), g_cb = spmv_grid(c->n_bnd);
-    const bool fused = c->p2p && c->ll_fused && !stencil;
-    const bool merged = !c->single() && !stencil && (fused || (!c->p2p && !(c->comm->stream_ordered() && c->overlap) && c->glist_all));
-    const unsigned g_sall = sell_grid(c->ng_int + c->ng_bnd, a.groups_per_wg);
-    red.expected = merged ? g_sall + g_ci + g_cb : g_si + g_ci + g_sb + g_cb;
-    red.slot_base = 0;
-    if (red.tail_seq) {
-        // The tail finish keeps the group's last min(expected, kShards) workgroups IN LAUNCH ORDER behind to add the slots. All of
-        // them must belong to the launch that comes last on this stream: a stayer of an earlier launch would wait for slots that
-        // only a later launch writes, and that launch cannot start behind it. So a group whose workgroups come from several
-        // launches, the last of them smaller than that, closes by arrival tickets instead -- same slots, same shard membership,
-        // same order of every sum, hence the same bits. (The launch with the exchange inside never carries a tail finish.)
-        const unsigned grids[4] = {merged ? g_sall : g_si, g_ci, merged || c->single() ? 0u : g_sb, c->single() ? 0u : g_cb};
-        unsigned launches = 0, last = 0;
-        for (unsigned g : grids)
-            if (g) { ++launches; last = g; }
-        if (launches > 1 && last < std::min<unsigned>(red.expected, (unsigned)kShards)) red.tail_seq = 0;
-    }
+
+    const SpmvShape shape = spmv_shape(c);
+    SpmvCall call;
+    call.ndot = ndot; call.epi = epi; call.has_shift = a.has_shift != 0; call.tail = red.tail_seq != 0; call.wave = red.wave != 0;
+    const SpmvPlan plan = spmv_plan(shape, call);
+    if (plan.error) die("internal", spmv_plan_error(plan.error));
+    a.groups_per_wg = plan.groups_per_wg;
+    red.expected = plan.expected; red.slot_base = 0;
+    if (!plan.tail) red.tail_seq = 0;
     a.red = red;
-    if (red.hand) c->hand.nsh = std::min<unsigned>(red.expected, (unsigned)kShards);      // what the consuming kernel will find
-    if (red.wave && (ndot > 0 || epi)) c->grp.nparts = red.expected * (kBlock / 64);   // one partial per wavefront
+    if (red.hand) c->hand.nsh = plan.hand_nsh;
+    if (plan.sets_nparts) c->grp.nparts = plan.expected * (kBlock / 64);
 
     // per-kernel timing: every SpMV kernel of this call gets its own start/stop event pair
     const bool timed = c->time_kernels && c->tev_used + 8 <= (int)c->tev.size();
     bool any_timed = false;
-    auto ev = [&](int i) -> hipEvent_t { return timed ? c->tev[c->tev_used + i] : nullptr; };
-    auto took = [&](bool launched) {
-        if (launched) a.fin.seq = 0;          // the first kernel of this SpMV finished the open group
-        if (launched && timed) { c->tev_used += 2; any_timed = true; }
-    };
-
-    auto interior = [&]() {
-        a.glist = c->glist_int_identity ? nullptr : c->glist_int; a.nlist = c->ng_int; a.red.slot_base = 0;
-        if (stencil) {
-            // (the plan only selects tilings the kernel is built for, and the epilogue only with ticket reductions: a launch that
-            // is declined here would leave y unwritten and a ticket group waiting for partial sums that never come)
-            if (!launch_spmv_stencil(a, ndot, epi == 3 ? 1 : 0, c->sc, ev(0), ev(1)))
-                die("internal", "the plane-marching product declined a launch its plan had selected (lines per wavefront / reduction mode)");
-            took(true);
-        } else {
-            took(launch_spmv_sell(a, ndot, false, c->sc, ev(0), ev(1)));
+    auto run = [&](bool after_halo) {
+        for (int i = 0; i < plan.nsteps; ++i) {
+            if (plan.step[i].after_halo != after_halo) continue;
+            if (!launch_step(c, a, plan.step[i], ndot, epi, timed ? c->tev[c->tev_used] : nullptr, timed ? c->tev[c->tev_used + 1] : nullptr)) continue;
+            a.fin.seq = 0;          // the first kernel of this SpMV finished the open group
+            if (timed) { c->tev_used += 2; any_timed = true; }
         }
-        a.desc = c->desc_int; a.nlist = c->n_int; a.red.slot_base = g_si;
-        took(launch_spmv(a, ndot, false, c->sc, ev(0), ev(1)));
-    };
-    auto boundary = [&]() {
-        a.glist = c->glist_bnd; a.nlist = c->ng_bnd; a.red.slot_base = g_si + g_ci;
-        took(launch_spmv_sell(a, ndot, true, c->sc, ev(0), ev(1)));
-        a.desc = c->desc_bnd; a.nlist = c->n_bnd; a.red.slot_base = g_si + g_ci + g_sb;
-        took(launch_spmv(a, ndot, true, c->sc, ev(0), ev(1)));
     };
 
-    if (epi && !(c->glist_all && c->nblk == 0 && (c->single() || fused))) die("internal", "SpMV epilogue on a multi-launch SpMV");
-    // Epilogue launches publish one partial row per WAVEFRONT for 32 helper workgroups to add: beyond a few thousand
-    // workgroups that sum, not the matrix, sets the pace (16.8 M rows = 65 k workgroups: 4.6 instead of 1.25 ms per
-    // iteration), so a workgroup takes several 256-row groups. Ranks sharing a GPU (tests): every row workgroup of
-    // the launch waits for the scalars, all ranks' launches must fit on the GPU together.
-    const unsigned epi_cap = c->wg_cap ? c->wg_cap : 8192u;
-    if (epi && !stencil && c->ng_int + c->ng_bnd > epi_cap) {
-        const unsigned ng = c->ng_int + c->ng_bnd;
-        a.groups_per_wg = std::max<int>(a.groups_per_wg, (int)((ng + epi_cap - 1) / epi_cap));
-        red.expected = sell_grid(ng, a.groups_per_wg) + g_ci;
-        a.red.expected = red.expected;
-        c->grp.nparts = red.expected * (kBlock / 64);
+    const bool multi = !c->single(), host = hosted(c);
+    unsigned seq = 0;
+    bool send = true, joined_pending = false;
+    hipEvent_t landed = nullptr;
+    if (c->p2p) {
+        seq = p2p_next_exchange(c, Sh);
+        send = !(c->fault_after > 0 && seq >= (unsigned)c->fault_after);   // BICG_TEST="p2p-fault-after=n" (tests)
     }
-    if (c->single()) {
-        if (epi && !stencil) {
-            a.glist = nullptr; a.nlist = c->ng_int; a.red.slot_base = 0;
-            took(launch_spmv_sell_epi(a, epi, false, c->sc, ev(0), ev(1)));
-        } else {
-            interior();
-        }
-    } else if (c->p2p) {
-        // peer-to-peer: the send list is stored straight into the landing rings of the ranks that
-        // need it, the interior rows run while the values cross the links, one kernel decodes the
-        // ring slot into the halo tail of x, then the rows that touch the halo run
-        const unsigned seq = p2p_next_exchange(c, Sh);
-        const bool lose = c->fault_after > 0 && seq >= (unsigned)c->fault_after;   // BICG_TEST="p2p-fault-after=n" (tests)
-        if (fused) {
-            // ONE launch: leading workgroups push, the others multiply; halo-touching groups come last
-            // and read the landing ring directly
-            a.ll.ring = c->halo_ring; a.ll.halo = c->halo; a.ll.seq = seq;
-            a.ll.nsend = lose ? 0u : c->nsend;
-            a.ll.npush = c->nsend ? std::min<unsigned>((c->nsend + kBlock - 1) / kBlock, 64u) : 0u;
-            a.ll.first_bnd = c->ng_int;
-            a.ll.send_idx = c->send_idx; a.ll.dst0 = c->push_dst0; a.ll.dstride = c->push_stride;
-            a.ll.timeout_ticks = c->p2p->timeout_ticks;
-            a.glist = c->glist_ll; a.nlist = c->ng_int + c->ng_bnd; a.red.slot_base = 0;
-            if (epi) took(launch_spmv_sell_epi(a, epi, true, c->sc, ev(0), ev(1), true));
-            else took(launch_spmv_sell(a, ndot, true, c->sc, ev(0), ev(1), true));
-            a.glist = nullptr;
-            a.desc = c->desc_int; a.nlist = c->n_int; a.red.slot_base = g_sall;
-            took(launch_spmv(a, ndot, false, c->sc, ev(0), ev(1)));
-        } else {
-            if (!lose) launch_halo_push(xin, c->send_idx, c->nsend, c->push_dst0, c->push_stride, seq, Sh, c->sc);
-            interior();
-            launch_halo_unpack(c->halo_ring, c->halo, seq, xin + c->n_loc, Sh, c->p2p->timeout_ticks, c->sc);
-            boundary();
-        }
-        if (c->pend) {
-            c->pend = false;
-            launch_apply_p2p(c->S, c->pend_phase, c->pend_n, c->p2p->red_desc(c->pend_seq), c->p2p->timeout_ticks, c->sc);
-            c->halo_unsynced = 0;
-        }
-    } else {
-        const bool two_streams = c->comm->stream_ordered() && c->overlap;
-        hipEvent_t eh = nullptr;
-        c->cur_sub = 1; sec_remark(c);          // the exchange: the reference's "agv" section (src/matrix.c:432)
-        launch_halo_pack(xin, c->send_idx, c->nsend, c->sendbuf, Sh, c->sc);
-        if (two_streams) {
-            hipEvent_t ep = c->ev_pack[c->i_pack++ % kEvRing];
-            BICG_HIP(hipEventRecord(ep, c->sc));
-            BICG_HIP(hipStreamWaitEvent(c->sm, ep, 0));
-            ctx_exchange(c, c->sendbuf, c->scnt.data(), c->sdsp.data(), xin + c->n_loc, c->rcnt.data(), c->rdsp.data(), c->sm);
-            eh = c->ev_halo[c->i_halo++ % kEvRing];
-            BICG_HIP(hipEventRecord(eh, c->sm));
-        } else {
-            ctx_exchange(c, c->sendbuf, c->scnt.data(), c->sdsp.data(), xin + c->n_loc, c->rcnt.data(), c->rdsp.data(), c->sc);
-        }
-        c->cur_sub = 0; sec_remark(c);
-        bool joined_pending = false;
-        if (c->pend) {   // start the deferred all-reduce behind the halo traffic
+    if (plan.fused) {
+        // the exchange rides inside the first step's launch
+        a.ll.ring = c->halo_ring; a.ll.halo = c->halo; a.ll.seq = seq;
+        a.ll.nsend = send ? c->nsend : 0u;
+        a.ll.npush = c->nsend ? std::min<unsigned>((c->nsend + kBlock - 1) / kBlock, 64u) : 0u;
+        a.ll.first_bnd = c->ng_int;
+        a.ll.send_idx = c->send_idx; a.ll.dst0 = c->push_dst0; a.ll.dstride = c->push_stride;
+        a.ll.timeout_ticks = c->p2p->timeout_ticks;
+    } else if (multi) {
+        if (host) { c->cur_sub = 1; sec_remark(c); }      // the exchange: the reference's "agv" section (src/matrix.c:432)
+        landed = halo_start(c, xin, Sh, seq, send, shape.own_stream);
+        if (host) { c->cur_sub = 0; sec_remark(c); }
+        if (host && c->pend) {   // start the deferred all-reduce behind the halo traffic
             hipEvent_t after = c->pend_ev;
             c->pend = false;
             group_enqueue(c, c->pend_n, c->pend_phase, after);
             joined_pending = true;
         }
-        if (!two_streams && c->glist_all && !stencil) {
-            // nothing overlaps the exchange: one launch over ALL sliced-ELL groups (rows without offd
-            // entries simply find an empty offd range) instead of an interior + a boundary launch
-            a.glist = nullptr; a.nlist = c->ng_int + c->ng_bnd; a.red.slot_base = 0;
-            took(launch_spmv_sell(a, ndot, true, c->sc, ev(0), ev(1)));
-            a.desc = c->desc_int; a.nlist = c->n_int; a.red.slot_base = g_sall;
-            took(launch_spmv(a, ndot, false, c->sc, ev(0), ev(1)));
-            a.desc = c->desc_bnd; a.nlist = c->n_bnd; a.red.slot_base = g_sall + g_ci;
-            took(launch_spmv(a, ndot, true, c->sc, ev(0), ev(1)));
-        } else {
-            interior();
-            if (eh) BICG_HIP(hipStreamWaitEvent(c->sc, eh, 0));
-            c->cur_sub = 2; sec_remark(c);      // the rows that touch the halo: the reference's second mult() (src/matrix.c:440)
-            boundary();
-            c->cur_sub = 0; sec_remark(c);
-        }
-        if (joined_pending && c->pend_ev) {
-            BICG_HIP(hipStreamWaitEvent(c->sc, c->pend_ev, 0));
-            c->pend_ev = nullptr;
-        }
+    }
+    run(false);
+    if (multi && !plan.fused) halo_land(c, xin, Sh, seq, landed);
+    const bool second = host && !plan.merged;      // the rows that touch the halo: the reference's second mult() (src/matrix.c:440)
+    if (second) { c->cur_sub = 2; sec_remark(c); }
+    run(true);
+    if (second) { c->cur_sub = 0; sec_remark(c); }
+    if (c->p2p && c->pend) {
+        c->pend = false;
+        launch_apply_p2p(c->S, c->pend_phase, c->pend_n, c->p2p->red_desc(c->pend_seq), c->p2p->timeout_ticks, c->sc);
+        c->halo_unsynced = 0;
+    }
+    if (joined_pending && c->pend_ev) {
+        BICG_HIP(hipStreamWaitEvent(c->sc, c->pend_ev, 0));
+        c->pend_ev = nullptr;
     }
     if (a.fin.seq) {   // no SpMV kernel was launched (a rank without work): finish the group on its own
         Finish f = a.fin;
@@ -459,14 +432,8 @@ void spmv_grp(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u,
 void halo_only(bicg_ctx *c, double *xin)
 {
     if (c->single() || (c->halo == 0 && c->nsend == 0)) return;
-    if (c->p2p) {
-        const unsigned seq = p2p_next_exchange(c, c->S);
-        launch_halo_push(xin, c->send_idx, c->nsend, c->push_dst0, c->push_stride, seq, c->S, c->sc);
-        launch_halo_unpack(c->halo_ring, c->halo, seq, xin + c->n_loc, c->S, c->p2p->timeout_ticks, c->sc);
-        return;
-    }
-    launch_halo_pack(xin, c->send_idx, c->nsend, c->sendbuf, c->S, c->sc);
-    ctx_exchange(c, c->sendbuf, c->scnt.data(), c->sdsp.data(), xin + c->n_loc, c->rcnt.data(), c->rdsp.data(), c->sc);
+    const unsigned seq = c->p2p ? p2p_next_exchange(c, c->S) : 0u;
+    halo_land(c, xin, c->S, seq, halo_start(c, xin, c->S, seq, true, false));
 }
 
 // The halo exchange of a set: nvec <= kSpmmCols vectors c->stride apart, ONE pack launch, ONE transport exchange, ONE unpack launch

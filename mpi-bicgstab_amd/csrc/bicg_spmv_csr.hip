@@ -154,12 +154,12 @@ __global__ void __launch_bounds__(kBlock) k_spmv(SpmvArgs a)
 
 // One workgroup per row block: the hardware dispatcher balances the ~12k workgroups of a
 // Transport-sized matrix better than a persistent grid; beyond kSpmvMaxGrid row blocks the kernel's
-// loop strides.
-unsigned spmv_grid(uint32_t nlist)
-{
-    if (nlist == 0) return 0;
-    return nlist < (uint32_t)kSpmvMaxGrid ? nlist : (unsigned)kSpmvMaxGrid;
-}
+// loop strides. That grid is spmv_grid() (bicg_spmv_plan.cpp).
+//
+// Slot contract with the launch plan of the distributed product (spmv_plan, bicg_plan.h): workgroup b
+// of a launch publishes its dot partials in slot a.red.slot_base + b, and the plan numbers the slots
+// of the launches that share a dot group by adding up spmv_grid() and sell_grid(). The grid launched
+// below and the grid the plan counts must therefore be the same function.
 
 template <int NDOT, bool OFFD>
 static void launch_spmv_var(const SpmvArgs &a, hipStream_t st, hipEvent_t e0, hipEvent_t e1)

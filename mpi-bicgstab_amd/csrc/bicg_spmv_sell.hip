@@ -1,19 +1,9 @@
-// bicg_spmv_sell.hip -- the sliced-ELL product's host side: the grid, the choice of the layout's translation unit
+// bicg_spmv_sell.hip -- the sliced-ELL product's host side: the choice of the layout's translation unit
 // (bicg_spmv_sell_lay.hip, one per layout) and the code objects loaded at set-up. No kernel is instantiated here.
+// (the grid, sell_grid: bicg_spmv_plan.cpp)
 #include "bicg_spmv_sell.h"
 
 namespace bicg {
-
-// workgroups launched for ngroups 256-row groups: every workgroup gets the same number (+-1)
-unsigned sell_grid(uint32_t ngroups, int per_wg)
-{
-    if (ngroups == 0) return 0;
-    if (per_wg < 1) per_wg = 1;
-    const unsigned per = (unsigned)per_wg;
-    const unsigned grid0 = (ngroups + per - 1) / per;             // upper bound on workgroups
-    const unsigned each = (ngroups + grid0 - 1) / grid0;
-    return (ngroups + each - 1) / each;
-}
 
 // The layouts, each instantiated in a translation unit of its own (the Makefile's SELL_LAYS names the same seven). The first
 // entry serves a layout value that is not in the list.

@@ -537,13 +537,7 @@ __global__ void __launch_bounds__(kBlock) k_spmv_stencil_w(SpmvArgs a)
     }
 }
 
-unsigned stencil_grid(const StencilDev &st)
-{
-    if (!st.on) return 0u;
-    const unsigned nyw = (st.ny + 4u * st.lines - 1u) / (4u * st.lines), nzb = (st.z_hi - st.z_lo + st.zl - 1u) / st.zl;
-    return (st.wide ? st.nxs / st.wide : st.nxs) * nyw * nzb;
-}
-
+// (the grid, stencil_grid: bicg_spmv_plan.cpp)
 template <class K>
 static void stencil_go(K kernel, const SpmvArgs &a, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
 {

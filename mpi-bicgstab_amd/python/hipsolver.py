@@ -71,7 +71,7 @@ EXPORTS = [
     "bicg_comm_init_single", "bicg_comm_finalize", "bicg_comm_selftest_rccl", "bicg_comm_rccl_loadable", "bicg_comm_last_error", "bicg_section_times", "bicg_comm_rank", "bicg_comm_size",
     "bicg_default_options", "bicg_create", "bicg_destroy", "bicg_solve", "bicg_load", "bicg_run", "bicg_fetch",
     "bicg_run_begin", "bicg_run_iterate", "bicg_run_iterate_timed", "bicg_run_end", "bicg_sync", "bicg_trace", "bicg_spmv", "bicg_dot", "bicg_spmv_bench", "bicg_plan_info", "bicg_ctx_flags", "bicg_spmm", "bicg_device_matrix_bytes", "bicg_uniform_entries", "bicg_constant_entries", "bicg_masked_rows", "bicg_stencil_info", "bicg_stencil_rows_per_lane", "bicg_comm_wait_stats", "bicg_plan_collisions", "bicg_product_kernels", "bicg_spmv_matrix_bytes", "bicg_last_shifted_persistent", "bicg_last_spmm_windowed", "bicg_dropin_context", "bicg_dropin_release", "bicg_dropin_stats",
-    "bicg_mtx_load_block", "bicg_mtx_free", "bicg_partition", "bicg_halo_plan", "bicg_halo_send_counts", "bicg_halo_send_lists", "bicg_row_blocks", "bicg_window_plan", "bicg_window_slot", "bicg_version", "bicg_has_experiments", "bicg_switch_value", "bicg_switch_unknown", "bicg_stream_bench", "bicg_create_device_csr", "bicg_stencil7_device", "bicg_device_free", "bicg_persist_plan", "bicg_set_plan_threads", "bicg_sell_plan_digest",
+    "bicg_mtx_load_block", "bicg_mtx_free", "bicg_partition", "bicg_halo_plan", "bicg_halo_send_counts", "bicg_halo_send_lists", "bicg_row_blocks", "bicg_window_plan", "bicg_window_slot", "bicg_version", "bicg_has_experiments", "bicg_switch_value", "bicg_switch_unknown", "bicg_stream_bench", "bicg_create_device_csr", "bicg_stencil7_device", "bicg_device_free", "bicg_persist_plan", "bicg_set_plan_threads", "bicg_sell_plan_digest", "bicg_spmv_launch_plan",
     "bicg_reorder_plan", "bicg_permute_block", "bicg_reorder_info",
     "bicg_solve_multi", "bicg_multi_trace", "bicg_comm_counts", "bicg_device_allocations",
     "bicg_update_values", "bicg_update_values_device", "bicg_persist_plan_sources", "bicg_dropin_refreshes",
@@ -965,6 +965,39 @@ def sell_plan_digest(blocks: HostBlocks, nranks: int = 1, rows_global: int | Non
         raise RuntimeError("bicg_sell_plan_digest failed")
     del keep
     return dict(zip(SELL_SUMMARY, (int(v) for v in summ))), dict(zip(SELL_ARRAYS, (int(v) for v in dig)))
+
+
+# bicg_spmv_launch_plan (include/bicgstab_hip.h section 5): names of the entries of its four arrays
+SPMV_SHAPE = ("ng_int", "ng_bnd", "n_int", "n_bnd", "nblk", "glist_all", "transport", "ll_fused", "has_send", "own_stream", "stencil_ok",
+              "stencil_wgs", "sell_gpw", "sell_gpw_dots", "wg_cap")
+SPMV_CALL = ("ndot", "epi", "has_shift", "tail", "wave")
+SPMV_PLAN = ("error", "groups_per_wg", "stencil", "fused", "merged", "expected", "hand_nsh", "sets_nparts", "tail", "nsteps")
+SPMV_STEP = ("family", "list", "nlist", "with_offd", "fused_halo", "slot_base", "after_halo")
+SPMV_TRANSPORTS = ("single", "p2p", "hosted")
+SPMV_FAMILIES = ("sell", "sell_epi", "stencil", "csr")
+SPMV_LISTS = ("all", "int", "bnd", "fused", "blk_int", "blk_bnd")
+
+
+def spmv_launch_plan(shape: dict, call: dict):
+    """The launch plan of one distributed product (bicg_spmv_launch_plan; no GPU, no context): shape keyed by SPMV_SHAPE, call by
+    SPMV_CALL (missing entries: 0; sell_gpw / sell_gpw_dots: 1) -> (plan dict keyed by SPMV_PLAN, list of step dicts keyed by
+    SPMV_STEP, in launch order)."""
+    L = lib()
+    _uip = C.POINTER(C.c_uint)
+    L.bicg_spmv_launch_plan.argtypes = [_uip, C.POINTER(C.c_int), _uip, _uip]
+    L.bicg_spmv_launch_plan.restype = C.c_int
+    unknown = (set(shape) - set(SPMV_SHAPE)) | (set(call) - set(SPMV_CALL))
+    if unknown:
+        raise KeyError(f"not an entry of the shape / the call: {sorted(unknown)}")
+    dflt = {"sell_gpw": 1, "sell_gpw_dots": 1}
+    sh = (C.c_uint * len(SPMV_SHAPE))(*(int(shape.get(k, dflt.get(k, 0))) for k in SPMV_SHAPE))
+    ca = (C.c_int * len(SPMV_CALL))(*(int(call.get(k, 0)) for k in SPMV_CALL))
+    pl, st = (C.c_uint * len(SPMV_PLAN))(), (C.c_uint * (4 * len(SPMV_STEP)))()
+    if L.bicg_spmv_launch_plan(sh, ca, pl, st) != 0:
+        raise RuntimeError("bicg_spmv_launch_plan failed")
+    plan = dict(zip(SPMV_PLAN, (int(v) for v in pl)))
+    n = len(SPMV_STEP)
+    return plan, [dict(zip(SPMV_STEP, (int(v) for v in st[i * n:(i + 1) * n]))) for i in range(plan["nsteps"])]
 
 
 # bicg_reorder_plan (include/bicgstab_hip.h section 5): names of its stats
