@@ -284,7 +284,7 @@ int bicg_update_values_device(bicg_ctx *ctx, const double *diag_val_d, const dou
  * check_every are BICG_BICGSTAB's. On a context WITHOUT a preconditioner these calls return -2 and touch nothing. Across ranks the
  * call is collective as for BICG_BICGSTAB; that every rank has installed its part is the caller's contract. It allocates nothing
  * beyond 1/d: the hat vectors live in work vectors the plain iteration leaves idle.
- * Out of scope: bicg_solve_multi* keeps refusing every method but BICG_BICGSTAB, and the CA, pipelined and shifted iterations have
+ * bicg_solve_multi / bicg_solve_multi_device accept it too (see there). Out of scope: the CA, pipelined and shifted iterations have
  * no preconditioned form. */
 int bicg_precond_diagonal(bicg_ctx *ctx, const double *d_loc);                       /* host array   */
 int bicg_precond_diagonal_device(bicg_ctx *ctx, const double *d_d, void *stream);    /* device array */
@@ -319,8 +319,9 @@ int bicg_precond_kind(bicg_ctx *ctx);
  * detection and check_every are BICG_BICGSTAB's. With bs = 1, or with blocks that hold d on their diagonals and zeros elsewhere, it is
  * bit-identical to method 4 with that d (as long as no entry of p or q is a zero, whose sign the two forms may render differently).
  * Method 5 on a context whose kind is not 2 returns -2 and touches nothing, as method 4 does on one whose kind is not 1.
- * Out of scope: forming the hat vectors in the pass that produces p or q, bicg_solve_multi*, the CA / pipelined / shifted iterations,
- * blocks of varying size. */
+ * bicg_solve_multi / bicg_solve_multi_device accept method 5 as well (see there): one launch per application for a whole set.
+ * Out of scope: forming the hat vectors in the pass that produces p or q, the CA / pipelined / shifted iterations, blocks of
+ * varying size. */
 int bicg_precond_block_diagonal(bicg_ctx *ctx, const double *blocks, int bs);                          /* host array   */
 int bicg_precond_block_diagonal_device(bicg_ctx *ctx, const double *blocks_d, int bs, void *stream);   /* device array */
 
@@ -386,8 +387,10 @@ int bicg_shifted_residuals(bicg_ctx *ctx, const double *x_loc_set, const double 
 int bicg_spmm(bicg_ctx *ctx, const double *x_loc_set, const double *sigma, int nvec, double *y_loc_set, double *ms_device);
 /* per-iteration trace of the last run (record_trace): arrays of length >= iterations, may be NULL */
 int bicg_trace(bicg_ctx *ctx, double *alpha, double *omega, double *beta, double *dot_r);
-/* Plain BiCGStab (BICG_BICGSTAB) on nrhs independent systems A x_j = b_j that share the resident matrix: one SpMM per product
- * for up to 16 columns, every column with its own alpha / omega / beta and its own convergence test.
+/* Plain BiCGStab on nrhs independent systems A x_j = b_j that share the resident matrix: one SpMM per product for up to 16
+ * columns, every column with its own alpha / omega / beta and its own convergence test. Methods: BICG_BICGSTAB (0), and its
+ * right-preconditioned forms BICG_BICGSTAB_DIAG (4) on a context whose bicg_precond_kind is 1 and BICG_BICGSTAB_BLOCK (5) on one
+ * whose kind is 2 -- the preconditioned methods are described behind the plain one below.
  * x_loc_set / r_loc_set are column-major, [j * local_rows + i], like x_loc_set of the shifted solvers: in = x0_j and b_j, out =
  * the solution and the recursive residual of column j. Column j runs exactly the loop of reference src/solver.c:74-120 on
  * (x0_j, b_j), with the loop condition dot_r > tol*tol*dot_zero && k < max_iter evaluated per column ON THE DEVICE at every
@@ -398,7 +401,21 @@ int bicg_trace(bicg_ctx *ctx, double *alpha, double *omega, double *beta, double
  * opt->check_every iterations are enqueued between host reads of the columns' flags; opt->record_trace keeps alpha, omega, beta
  * and (r,r) per column and iteration for bicg_multi_trace (max_iter x 16 x 4 doubles per set). res (nrhs entries, may be NULL):
  * iterations, dot_r, dot_zero and breakdown_iteration of column j; the time fields of every entry are those of the whole call.
- * Returns the largest k_j; -2 for a method other than BICG_BICGSTAB or nrhs < 1 -- a refused call touches nothing.
+ * Returns the largest k_j; -2 for methods 1-3, for method 4 or 5 on a context whose bicg_precond_kind is not that method's (1 / 2),
+ * or for nrhs < 1 -- a refused call touches nothing: neither x, r, the trace nor any allocation.
+ * METHODS 4 AND 5: column j runs exactly the right-preconditioned iteration bicg_solve runs for that method on (x0_j, b_j): the two
+ * products take P^ = M^-1 P and Q^ = M^-1 Q, x += alpha p^ + omega q^, r stays the residual of the caller's system, and the loop
+ * condition, freezing, check_every, record_trace, bicg_multi_trace, the res entries, sets of 16 with a partial last one, the per-column
+ * product fallback and the collective rules below are the plain call's. With d = 1, or identity blocks of any bs, every column is
+ * bit-identical to the plain call. The preconditioner is read as installed at the time of the call: one re-installed or replaced
+ * between two calls takes effect in the second. Launches: method 4 makes the plain call's, the hat vectors being written by the
+ * passes that produce p and q; method 5 adds ONE launch per application for the whole set (k_bjac_apply_set: a row's bs plane
+ * entries are loaded once for the 16 columns; every column gets the bytes bicg_precond_apply gives on it; frozen columns are neither
+ * read nor written), i.e. two launches per iteration and set, and one behind the set-up phase. Memory: the first preconditioned
+ * call on a context makes ONE more allocation, the two hat sets (2 x 16 vectors, 32 x 8 bytes per row), zeroed once; later calls of
+ * any method allocate nothing; bicg_destroy releases it.
+ * Across ranks a rank whose context lacks the method's preconditioner returns -2 and the other ranks return -1, nothing is touched
+ * anywhere (the rule for ld < local_rows of bicg_solve_multi_device); bs and the blocks are a rank's own and need not agree.
  * The products are SpMMs that read P and R in place where bicg_spmm is available (BICG_FLAG_SPMM) and one bicg_spmv-style product
  * per active column otherwise, or under BICG_PLAN="spmm=0" (read at the call). Memory: the first call allocates six sets of 16
  * vectors beside the SpMM's own buffers -- 96 x 8 bytes per row, about 1.2 GB at 1.6 M rows --, released by bicg_destroy.
@@ -472,6 +489,10 @@ int bicg_precond_apply(bicg_ctx *ctx, const double *v_loc, double *z_loc);
 /* reps back-to-back applications of the installed preconditioner on device-resident vectors; returns average ms per application
  * (HIP events on the library's compute stream), as bicg_spmv_bench does for the product. 0 done, -2 none installed. */
 int bicg_precond_apply_bench(bicg_ctx *ctx, int reps, double *ms_per_apply);
+/* the same for the set application of bicg_solve_multi's method 5: ncols (1..16) columns per launch, average ms per launch. chunk:
+ * columns a workgroup walks, 4, 8 or 16, anything else the library's choice -- for measuring that choice. 0 done; -2 no block
+ * preconditioner installed, or ncols out of range. Allocates what a first preconditioned bicg_solve_multi call allocates. */
+int bicg_precond_apply_set_bench(bicg_ctx *ctx, int ncols, int chunk, int reps, double *ms_per_apply);
 double bicg_dot(bicg_ctx *ctx, const double *x_loc, const double *y_loc);
 /* reps back-to-back SpMVs on device-resident vectors; returns average ms per SpMV (HIP events on
  * the library's compute stream) */

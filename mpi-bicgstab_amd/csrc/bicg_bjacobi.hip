@@ -9,6 +9,7 @@
 //                   read straight from `in` (a block's mates are neighbours in memory: the lanes of a wavefront share their lines).
 //                   acc = m_0 v_0, then acc = fma(m_j, v_j, acc) for j ascending over the block's rows -- the same for every grid
 //                   shape, rank count and layout. A block may straddle wavefronts and workgroups: no lane depends on another.
+//   k_bjac_apply_set  the same on the columns of a multi-RHS set in one launch, a row's plane entries loaded once for the set (below)
 // A reordered context keeps the blocks the caller's: context row i belongs to block perm[i] / bs and finds its mates through inv.
 // Vector loads and stores only. gfx950 only.
 #include "bicg_device.h"
@@ -115,6 +116,82 @@ void apply_bs(const double *minv, size_t stride, const uint32_t *perm, const uin
     else hipLaunchKernelGGL((k_bjac_apply<BS, false>), dim3(grid), dim3(kThreads), 0, st, minv, stride, perm, inv, in, out, n);
 }
 
+// k_bjac_apply on the columns of a multi-RHS set (bicg_solve_multi, method 5) in ONE launch: column c of in / out starts at
+// c vstride. A thread owns one row: its BS plane entries, and on a reordered context its BS mate indices, are loaded ONCE and stay in
+// registers while it walks the CH columns blockIdx.y selects -- the planes cost 8 BS bytes per row and chunk instead of per column.
+// The mate loads of FLY columns are in flight before the first fma. A column's sum is k_bjac_apply's, term for term: the same bytes.
+// A column whose flag S->active is 0 is neither read nor written; the flags are workgroup-uniform and read once, before any vector.
+template <int BS, bool RO, int CH>
+__global__ void __launch_bounds__(kThreads) k_bjac_apply_set(const double *__restrict__ minv, size_t stride, const uint32_t *__restrict__ perm,
+                                                             const uint32_t *__restrict__ inv, const double *__restrict__ in,
+                                                             double *__restrict__ out, size_t vstride, uint32_t n, int nv,
+                                                             const MultiScal *__restrict__ S)
+{
+    constexpr int FLY = BS <= 4 ? (CH < 8 ? CH : 8) : BS <= 8 ? 4 : 2;      // columns in flight: at most 32 mates in registers
+    static_assert(CH % FLY == 0 && CH <= kSpmmCols, "a chunk is whole groups of FLY columns");
+    const int c0 = (int)blockIdx.y * CH;
+    unsigned live = 0;
+#pragma unroll
+    for (int c = 0; c < CH; ++c)
+        if (c0 + c < nv && S->active[c0 + c]) live |= 1u << c;
+    if (!live) return;
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t o = RO ? perm[i] : i;
+    const uint32_t base = (o / (uint32_t)BS) * (uint32_t)BS;     // the block's first row, caller's numbering
+    const uint32_t m = min((uint32_t)BS, n - base);
+    double mv[BS];
+    uint32_t at[BS];                                             // the mates in the context's numbering (0 beyond a partial block: not read)
+#pragma unroll
+    for (int j = 0; j < BS; ++j) mv[j] = minv[(size_t)j * stride + i];
+#pragma unroll
+    for (int j = 0; j < BS; ++j) {
+        const uint32_t mate = base + (uint32_t)j;
+        at[j] = (uint32_t)j < m ? (RO ? inv[mate] : mate) : 0u;
+    }
+#pragma unroll
+    for (int g = 0; g < CH; g += FLY) {
+        if (!((live >> g) & ((1u << FLY) - 1u))) continue;
+        double vv[FLY][BS];
+#pragma unroll
+        for (int f = 0; f < FLY; ++f) {
+            const double *col = in + (size_t)(c0 + g + f) * vstride;
+#pragma unroll
+            for (int j = 0; j < BS; ++j) vv[f][j] = ((live >> (g + f)) & 1u) && (uint32_t)j < m ? col[at[j]] : 0.0;
+        }
+#pragma unroll
+        for (int f = 0; f < FLY; ++f) {
+            if (!((live >> (g + f)) & 1u)) continue;
+            double acc = mv[0] * vv[f][0];
+#pragma unroll
+            for (int j = 1; j < BS; ++j)
+                if ((uint32_t)j < m) acc = fma(mv[j], vv[f][j], acc);
+            out[(size_t)(c0 + g + f) * vstride + i] = acc;
+        }
+    }
+}
+
+template <int BS, int CH>
+void apply_set_ch(const double *minv, size_t stride, const uint32_t *perm, const uint32_t *inv, const double *in, double *out, size_t vstride,
+                  uint32_t n, int nv, const MultiScal *S, hipStream_t st)
+{
+    const dim3 grid((unsigned)(((uint64_t)n + kThreads - 1) / kThreads), (unsigned)((nv + CH - 1) / CH));
+    if (perm) hipLaunchKernelGGL((k_bjac_apply_set<BS, true, CH>), grid, dim3(kThreads), 0, st, minv, stride, perm, inv, in, out, vstride, n, nv, S);
+    else hipLaunchKernelGGL((k_bjac_apply_set<BS, false, CH>), grid, dim3(kThreads), 0, st, minv, stride, perm, inv, in, out, vstride, n, nv, S);
+}
+
+template <int BS>
+void apply_set_bs(const double *minv, size_t stride, const uint32_t *perm, const uint32_t *inv, const double *in, double *out, size_t vstride,
+                  uint32_t n, int nv, const MultiScal *S, int chunk, hipStream_t st)
+{
+    switch (chunk) {
+    case 4:  apply_set_ch<BS, 4>(minv, stride, perm, inv, in, out, vstride, n, nv, S, st); break;
+    case 8:  apply_set_ch<BS, 8>(minv, stride, perm, inv, in, out, vstride, n, nv, S, st); break;
+    case 16: apply_set_ch<BS, 16>(minv, stride, perm, inv, in, out, vstride, n, nv, S, st); break;
+    default: apply_set_ch<BS, bjac_set_chunk(BS)>(minv, stride, perm, inv, in, out, vstride, n, nv, S, st); break;
+    }
+}
+
 }  // namespace
 
 void launch_bjac_invert(const double *blocks, uint32_t n, int bs, double *work, int *flag, hipStream_t st)
@@ -142,6 +219,19 @@ void launch_bjac_apply(const double *minv, size_t stride, int bs, const uint32_t
     BICG_BJAC_CASE(9) BICG_BJAC_CASE(10) BICG_BJAC_CASE(11) BICG_BJAC_CASE(12) BICG_BJAC_CASE(13) BICG_BJAC_CASE(14) BICG_BJAC_CASE(15) BICG_BJAC_CASE(16)
 #undef BICG_BJAC_CASE
     default: break;      // (the installer admits 1 .. 16 only)
+    }
+}
+
+void launch_bjac_apply_set(const double *minv, size_t stride, int bs, const uint32_t *perm, const uint32_t *inv, const double *in, double *out,
+                           size_t vstride, uint32_t n, int nv, const MultiScal *S, int chunk, hipStream_t st)
+{
+    if (n == 0 || nv < 1) return;
+    switch (bs) {
+#define BICG_BJAC_CASE(B) case B: apply_set_bs<B>(minv, stride, perm, inv, in, out, vstride, n, nv, S, chunk, st); break;
+    BICG_BJAC_CASE(1) BICG_BJAC_CASE(2) BICG_BJAC_CASE(3) BICG_BJAC_CASE(4) BICG_BJAC_CASE(5) BICG_BJAC_CASE(6) BICG_BJAC_CASE(7) BICG_BJAC_CASE(8)
+    BICG_BJAC_CASE(9) BICG_BJAC_CASE(10) BICG_BJAC_CASE(11) BICG_BJAC_CASE(12) BICG_BJAC_CASE(13) BICG_BJAC_CASE(14) BICG_BJAC_CASE(15) BICG_BJAC_CASE(16)
+#undef BICG_BJAC_CASE
+    default: break;
     }
 }
 

@@ -511,10 +511,14 @@ struct SpmmArgs {
 
 // Multi-RHS plain BiCGStab (bicg_multi.hip, bicg_multi.cpp): one set of up to kSpmmCols independent recurrences on the resident
 // matrix. The six vector sets hold their columns `stride` apart; the scalars of every column live in one block per set.
+// Right-preconditioned (methods 4 and 5): two more sets, the hat vectors P^ = M^-1 P and Q^ = M^-1 Q the
+// products read (null in a plain call), and for the diagonal 1 / d -- ONE plane of n doubles shared by every column.
 struct MultiVecs {
     double *x, *r, *rh, *p, *s, *y;
     size_t stride;
     uint32_t n;
+    double *ph, *qh;
+    const double *dinv;
 };
 struct MultiScal {
     double rTr[kSpmmCols], rTr_old[kSpmmCols], alpha[kSpmmCols], omega[kSpmmCols], beta[kSpmmCols];
@@ -594,6 +598,12 @@ void launch_multi_q(const MultiVecs &v, int nv, MultiScal *S, hipStream_t st);  
 void launch_multi_dot_qy(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st);   // (q,y), (y,y)
 void launch_multi_xr(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st);       // x, r updates ; (r,r), (r#,r)
 void launch_multi_p(const MultiVecs &v, int nv, MultiScal *S, hipStream_t st);                      // p = beta p + r - beta omega s
+// ... and the phases of the right-preconditioned iteration: the same grids, dots and sums. _diag: the pass also writes the hat vector
+// of what it produces, v.dinv o (p or q); launch_multi_xr_hat (either preconditioner): x = (x + alpha p^) + omega q^
+void launch_multi_init_diag(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st);   // ... ; p^ = dinv o p
+void launch_multi_q_diag(const MultiVecs &v, int nv, MultiScal *S, hipStream_t st);                    // ... ; q^ = dinv o q
+void launch_multi_xr_hat(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st);
+void launch_multi_p_diag(const MultiVecs &v, int nv, MultiScal *S, hipStream_t st);                    // ... ; p^ = dinv o p
 void launch_multi_finish(int phase, int nv, MultiScal *S, const double *part, unsigned nwg, hipStream_t st);
 // the finish across ranks: this rank's sums of all kSpmmCols columns into its row of red[nranks][2][kSpmmCols] (the other rows
 // zeroed), and -- after the all-reduce of red -- the rows added in a fixed order (rank_tree_sum's) and the recurrence applied, one thread per column
@@ -629,6 +639,14 @@ void launch_bjac_planes(const double *work, const uint32_t *perm, uint32_t n, in
 // or neither
 void launch_bjac_apply(const double *minv, size_t stride, int bs, const uint32_t *perm, const uint32_t *inv, const double *in, double *out,
                        uint32_t n, hipStream_t st);
+// the same for the nv <= kSpmmCols columns of a set in ONE launch (bicg_solve_multi, method 5): column j of in / out starts at
+// j vstride; a row's plane entries are loaded once for the whole set; a column whose S->active flag is 0 is neither read nor
+// written; every column gets the bytes launch_bjac_apply gives on it. chunk: columns a workgroup walks -- 4, 8 or 16 for
+// measurements, anything else bjac_set_chunk(bs), what measured best on one MI355X at 1.6 M rows (profiles/NOTES.md: 16 columns at
+// bs = 4, 8 and 16, where the planes dominate the bytes; 4 at bs = 1, where they do not and more workgroups win; 2 and 3 were not timed)
+constexpr int bjac_set_chunk(int bs) { return bs == 1 ? 4 : 16; }
+void launch_bjac_apply_set(const double *minv, size_t stride, int bs, const uint32_t *perm, const uint32_t *inv, const double *in, double *out,
+                           size_t vstride, uint32_t n, int nv, const MultiScal *S, int chunk, hipStream_t st);
 // bicg_refresh.hip
 // new values for the resident matrix (bicg_update_values). RefreshSrc: the caller's values in the CSR order of the block handed to
 // bicg_create; the context's row r starts at val[ptr[rowmap ? rowmap[r] : r]] (rowmap: perm of a reordered context, ptr then the

@@ -325,6 +325,7 @@ struct bicg_ctx {
     // kept on the host for bicg_multi_trace: [column][4][mt_iters[column]]
     double *mt_slab = nullptr, *mt_part = nullptr, *mt_trace = nullptr;
     MultiScal *mt_S = nullptr;
+    double *mt_hat = nullptr;              // P^ and Q^, two more sets: one allocation of its own, made by the first preconditioned call (methods 4, 5)
     double *mt_red = nullptr;              // [nranks][2][kSpmmCols]: every rank's local dot sums, gathered by one all-reduce (k_multi_sum)
     int mt_trace_cap = 0;
     std::vector<std::vector<double>> mt_host_trace;
@@ -548,6 +549,8 @@ void persist_account(bicg_ctx *c);
 bool persist_chunk_shifted(bicg_ctx *c, int mode, int niter, int it0, int nsig, int seed, double shift);
 // ---- the context's preconditioner (bicg_precond.cpp)
 void precond_apply(bicg_ctx *c, const double *in, double *out);      // out = M^-1 in, one launch on the compute stream
+// ... and on the nv columns of a multi-RHS set whose flag S->active is up, c->stride apart: still one launch (BLOCK only; chunk: launch_bjac_apply_set)
+void precond_apply_set(bicg_ctx *c, const double *in, double *out, int nv, const MultiScal *S, int chunk = 0);
 // a preconditioned method on a context that does not hold ITS preconditioner: the solving calls return -2 and touch nothing
 inline bool diag_refused(const bicg_ctx *c, int method) { return c && precond_kind_of(method) != Precond::NONE && c->pc.kind != precond_kind_of(method); }
 // ---- drop-in entry points (bicg_dropin.cpp)

@@ -9,6 +9,13 @@
 // The loop condition of a column is evaluated by the last finish ON THE DEVICE at every iteration; the workgroups of a column
 // whose condition is false return at once, so its x and r stay as they are. The host reads the flags every check_every iterations.
 //
+// Right-preconditioned (methods 4 and 5 on a context that holds the matching preconditioner): every column
+// runs Driver::iter_plain's preconditioned form (bicg_solver.cpp). Two more sets, P^ = M^-1 P and Q^ = M^-1 Q (mt_hat, an allocation
+// of its own made by the first such call), are what the two products read; x += alpha p^ + omega q^; r stays the residual of the
+// caller's system, so the dots, the scalars and the loop condition are the plain call's. DIAGONAL: the passes that produce p and q
+// write the hat vectors too -- the plain call's launch sequence. BLOCK: one k_bjac_apply_set launch for the whole set behind each of
+// them (and one behind the set-up phase): two launches more per iteration and set. The planes are read as installed at the call.
+//
 // Across ranks (nranks > 1) the call is collective. Every product of a set is one spmm_pass -- ONE halo exchange for the set
 // (halo_set) -- or, without the SpMM, one collective spmv() per column the agreed flags show as live. Every finish is k_multi_sum,
 // ONE all-reduce of mt_red[nranks][2][kSpmmCols] that gathers the ranks' local sums (each rank's row is added to zeros only), and
@@ -35,11 +42,26 @@ void multi_buffers(bicg_ctx *c)
     BICG_HIP(hipDeviceSynchronize());      // the memset ran on the null stream: c->sc does not wait for it
 }
 
-MultiVecs multi_vecs(const bicg_ctx *c)
+// P^ and Q^ of the right-preconditioned methods: ONE more allocation, made by the first such call on the context and zeroed once
+// (halo tails, padding rows and unused columns stay finite), with mt_slab's 64 doubles of slack: the products read these two sets
+void multi_hat_buffers(bicg_ctx *c)
+{
+    if (c->mt_hat) return;
+    const size_t slab = 2 * (size_t)kSpmmCols * c->stride + 64;
+    c->mt_hat = c->own.alloc<double>(slab);
+    BICG_HIP(hipMemset(c->mt_hat, 0, sizeof(double) * slab));
+    BICG_HIP(hipDeviceSynchronize());      // (the null stream again)
+}
+
+// hat: the preconditioner the call's method runs with -- the planes as they are installed NOW
+MultiVecs multi_vecs(const bicg_ctx *c, Precond::Kind hat)
 {
     const size_t set = (size_t)kSpmmCols * c->stride;
     double *b = c->mt_slab;
-    return MultiVecs{b, b + set, b + 2 * set, b + 3 * set, b + 4 * set, b + 5 * set, c->stride, c->n_loc};
+    MultiVecs v{b, b + set, b + 2 * set, b + 3 * set, b + 4 * set, b + 5 * set, c->stride, c->n_loc, nullptr, nullptr, nullptr};
+    if (hat != Precond::NONE) { v.ph = c->mt_hat; v.qh = c->mt_hat + set; }
+    if (hat == Precond::DIAGONAL) v.dinv = c->pc.planes;
+    return v;
 }
 
 // out = A in for the nv columns of a set (`live`: the columns the host still knows to be active; a frozen column's product is
@@ -119,11 +141,15 @@ int solve_multi_any(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_se
         // collective from here on: a rank whose own arguments are refusable still takes part in the check, or the others would wait
         use_device(c);
         multi_red_buffer(c);
-        const bool bad = device && !c->phantom && (!x_loc_set || !r_loc_set || ld < c->n_loc);
+        // (... and a rank without the method's preconditioner: bs and the blocks are a rank's own, that one is installed is not)
+        const bool bad = (device && !c->phantom && (!x_loc_set || !r_loc_set || ld < c->n_loc)) || diag_refused(c, method);
         if (!multi_agree(c, method, nrhs, o, c->spmm_ok && !plan_off("spmm"), bad) && !bad) return -1;
     }
     if (device && !c->phantom && (!x_loc_set || !r_loc_set)) return -1;
-    if (method != BICG_BICGSTAB || nrhs < 1 || (device && !c->phantom && ld < c->n_loc)) return -2;
+    // plain BiCGStab, as it stands or right-preconditioned with the preconditioner the context holds
+    const Precond::Kind hat = precond_kind_of(method);
+    if ((method != BICG_BICGSTAB && hat == Precond::NONE) || diag_refused(c, method)) return -2;
+    if (nrhs < 1 || (device && !c->phantom && ld < c->n_loc)) return -2;
     use_device(c);
     std::vector<double> ph_x, ph_r;        // a context without rows holds one phantom row: zeros in, nothing out (host_in)
     if (c->phantom && !device) { ph_x.assign((size_t)nrhs, 0.0); ph_r.assign((size_t)nrhs, 0.0); x_loc_set = ph_x.data(); r_loc_set = ph_r.data(); }
@@ -133,6 +159,7 @@ int solve_multi_any(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_se
     const bool spmm = c->spmm_ok && !plan_off("spmm");
     if (spmm) spmm_buffers(c);
     multi_buffers(c);
+    if (hat != Precond::NONE) multi_hat_buffers(c);
     const bool tracing = o.record_trace != 0 && o.max_iter > 0;
     if (tracing && c->mt_trace_cap < o.max_iter) {
         c->mt_trace_cap = o.max_iter;
@@ -141,7 +168,8 @@ int solve_multi_any(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_se
     c->mt_host_trace.clear(); c->mt_iters.clear();
     if (tracing) { c->mt_host_trace.resize((size_t)nrhs); c->mt_iters.assign((size_t)nrhs, 0); }
 
-    const MultiVecs v = multi_vecs(c);
+    const MultiVecs v = multi_vecs(c, hat);
+    double *const in_p = hat ? v.ph : v.p, *const in_q = hat ? v.qh : v.r;      // what the two products of an iteration read
     const size_t n = c->n_loc;
     const unsigned nwg = multi_grid(c->n_loc);
     MultiScal h;
@@ -170,8 +198,10 @@ int solve_multi_any(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_se
         int live[kSpmmCols];
         for (int j = 0; j < kSpmmCols; ++j) live[j] = j < nv;
         multi_product(c, spmm, v.x, v.s, nv, live);
-        launch_multi_init(v, nv, c->mt_S, c->mt_part, c->sc);
+        if (hat == Precond::DIAGONAL) launch_multi_init_diag(v, nv, c->mt_S, c->mt_part, c->sc);   // ... ; p^ = dinv o p
+        else launch_multi_init(v, nv, c->mt_S, c->mt_part, c->sc);
         multi_finish(c, MP_INIT, nv, nwg);
+        if (hat == Precond::BLOCK) precond_apply_set(c, v.p, v.ph, nv, c->mt_S);                   // p^ = M^-1 p, the columns the finish left active
         fetch_multi(c, &h);
         const double t1 = now_sec();
 
@@ -182,16 +212,21 @@ int solve_multi_any(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_se
             if (!any) break;
             const int chunk = std::min(o.check_every, o.max_iter - it);
             for (int i = 0; i < chunk; ++i) {
-                multi_product(c, spmm, v.p, v.s, nv, live);                              // s = A p
+                multi_product(c, spmm, in_p, v.s, nv, live);                             // s = A p (A p^)
                 launch_multi_dot_rs(v, nv, c->mt_S, c->mt_part, c->sc);                  // (r#,s)
                 multi_finish(c, MP_ALPHA, nv, nwg);
-                launch_multi_q(v, nv, c->mt_S, c->sc);                                   // q = r - alpha s (kept in r)
-                multi_product(c, spmm, v.r, v.y, nv, live);                              // y = A q
+                if (hat == Precond::DIAGONAL) launch_multi_q_diag(v, nv, c->mt_S, c->sc); // q = r - alpha s (kept in r) ; q^ = dinv o q
+                else launch_multi_q(v, nv, c->mt_S, c->sc);                              // q = r - alpha s (kept in r)
+                if (hat == Precond::BLOCK) precond_apply_set(c, v.r, v.qh, nv, c->mt_S); // q^ = M^-1 q
+                multi_product(c, spmm, in_q, v.y, nv, live);                             // y = A q (A q^)
                 launch_multi_dot_qy(v, nv, c->mt_S, c->mt_part, c->sc);                  // (q,y), (y,y)
                 multi_finish(c, MP_OMEGA, nv, nwg);
-                launch_multi_xr(v, nv, c->mt_S, c->mt_part, c->sc);                      // x, r ; (r,r), (r#,r)
+                if (hat) launch_multi_xr_hat(v, nv, c->mt_S, c->mt_part, c->sc);         // x += alpha p^ + omega q^, r ; (r,r), (r#,r)
+                else launch_multi_xr(v, nv, c->mt_S, c->mt_part, c->sc);                 // x, r ; (r,r), (r#,r)
                 multi_finish(c, MP_END, nv, nwg);
-                launch_multi_p(v, nv, c->mt_S, c->sc);                                   // p
+                if (hat == Precond::DIAGONAL) launch_multi_p_diag(v, nv, c->mt_S, c->sc); // p ; p^ = dinv o p
+                else launch_multi_p(v, nv, c->mt_S, c->sc);                              // p
+                if (hat == Precond::BLOCK) precond_apply_set(c, v.p, v.ph, nv, c->mt_S); // p^ = M^-1 p
             }
             it += chunk;
             fetch_multi(c, &h);
@@ -245,6 +280,38 @@ int bicg_solve_multi_device(bicg_ctx *c, int method, double *x_set_d, double *r_
                             bicg_result *res, void *stream)
 {
     return solve_multi_any(c, method, x_set_d, r_set_d, ld, nrhs, opt_in, res, true, (hipStream_t)stream);
+}
+
+// measurement only (tools/multi_precond_probe.py): `reps` set applications P -> P^ of the installed block preconditioner on ncols
+// columns of ones, back to back between two events, every column's flag up. chunk: launch_bjac_apply_set's. Not collective.
+int bicg_precond_apply_set_bench(bicg_ctx *c, int ncols, int chunk, int reps, double *ms_per_apply)
+{
+    if (!c || c->pc.kind != Precond::BLOCK || ncols < 1 || ncols > kSpmmCols || !ms_per_apply) return -2;
+    use_device(c);
+    multi_buffers(c);
+    multi_hat_buffers(c);
+    const MultiVecs v = multi_vecs(c, Precond::BLOCK);
+    MultiScal h;
+    memset(&h, 0, sizeof h);
+    for (int j = 0; j < ncols; ++j) h.active[j] = 1;
+    std::vector<double> ones(c->n_loc, 1.0);
+    BICG_HIP(hipMemcpyAsync(c->mt_S, &h, sizeof h, hipMemcpyHostToDevice, c->sc));
+    for (int j = 0; j < ncols; ++j)
+        BICG_HIP(hipMemcpyAsync(v.p + (size_t)j * c->stride, ones.data(), sizeof(double) * c->n_loc, hipMemcpyHostToDevice, c->sc));
+    BICG_HIP(hipStreamSynchronize(c->sc));
+    for (int i = 0; i < 3; ++i) precond_apply_set(c, v.p, v.ph, ncols, c->mt_S, chunk);
+    hipEvent_t a, b;
+    BICG_HIP(hipEventCreate(&a)); BICG_HIP(hipEventCreate(&b));
+    BICG_HIP(hipEventRecord(a, c->sc));
+    for (int i = 0; i < reps; ++i) precond_apply_set(c, v.p, v.ph, ncols, c->mt_S, chunk);
+    BICG_HIP(hipEventRecord(b, c->sc));
+    BICG_HIP(hipEventSynchronize(b));
+    BICG_HIP(hipGetLastError());
+    float ms = 0.f;
+    BICG_HIP(hipEventElapsedTime(&ms, a, b));
+    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
+    *ms_per_apply = (double)ms / (reps > 0 ? reps : 1);
+    return 0;
 }
 
 int bicg_multi_trace(bicg_ctx *c, int column, double *alpha, double *omega, double *beta, double *dot_r)

@@ -13,6 +13,9 @@
 //                       the column's place in the set.
 //   k_multi_sum<PH>, k_multi_apply<PH>  the finish across ranks, split around one all-reduce that acts as an all-gather (below).
 //
+// Methods 4 and 5 (right-preconditioned) run the same kernels with four more phases: no launch added for the
+// diagonal, whose hat vectors are written by the pass that produces p or q.
+//
 // Compiled with -ffp-contract=off like every unit: each daxpy / dscal of the reference stays a rounding of its own.
 #include "bicg_device.h"
 #include "bicg_devfn.h"
@@ -50,11 +53,16 @@ __device__ __forceinline__ pr axpy(pr y, double a, pr x) { return {y.a + a * x.a
 __device__ __forceinline__ pr scal(double a, pr x) { return {a * x.a, a * x.b}; }
 __device__ __forceinline__ double dot2(pr x, pr y) { return x.a * y.a + x.b * y.b; }
 
-enum MultiVecPhase { MV_INIT = 0, MV_DOT_RS = 1, MV_Q = 2, MV_DOT_QY = 3, MV_XR = 4, MV_P = 5 };
-template <int PH> struct mv_dots { static constexpr int value = (PH == MV_INIT || PH == MV_DOT_RS) ? 1 : (PH == MV_DOT_QY || PH == MV_XR) ? 2 : 0; };
+// MV_*_D / MV_XR_H: the right-preconditioned forms (methods 4 and 5) of the phase they are named after -- what FInitDiag, FDiagQ,
+// FDiagXR and FDiagP (bicg_vec.hip) do for one vector. _D: the pass also writes the hat vector of what it produces, dinv o (p or q),
+// dinv ONE plane for every column (no column offset); MV_XR_H, for either preconditioner: x takes alpha p^ + omega q^.
+enum MultiVecPhase { MV_INIT = 0, MV_DOT_RS = 1, MV_Q = 2, MV_DOT_QY = 3, MV_XR = 4, MV_P = 5, MV_INIT_D = 6, MV_Q_D = 7, MV_XR_H = 8, MV_P_D = 9 };
+template <int PH> struct mv_dots {
+    static constexpr int value = (PH == MV_INIT || PH == MV_DOT_RS || PH == MV_INIT_D) ? 1 : (PH == MV_DOT_QY || PH == MV_XR || PH == MV_XR_H) ? 2 : 0;
+};
 
 // One element (T = double: the odd tail) or one 16-byte pair (T = pr) of phase PH: the loads of `In`, then the arithmetic.
-template <int PH, class T> struct In { T a, b, c, d, e; };
+template <int PH, class T> struct In { T a, b, c, d, e, f; };
 
 template <int PH> __device__ __forceinline__ In<PH, pr> fetch(const MultiVecs &v, size_t o, uint32_t i)
 {
@@ -65,6 +73,10 @@ template <int PH> __device__ __forceinline__ In<PH, pr> fetch(const MultiVecs &v
     if constexpr (PH == MV_DOT_QY) { in.a = ldp(v.r + o, i); in.b = ldp(v.y + o, i); }
     if constexpr (PH == MV_XR)     { in.a = ldp(v.r + o, i); in.b = ldp_nt(v.x + o, i); in.c = ldp(v.p + o, i); in.d = ldp(v.y + o, i); in.e = ldp(v.rh + o, i); }
     if constexpr (PH == MV_P)      { in.a = ldp(v.p + o, i); in.b = ldp(v.r + o, i); in.c = ldp(v.s + o, i); }
+    if constexpr (PH == MV_INIT_D) { in.a = ldp(v.r + o, i); in.b = ldp(v.s + o, i); in.c = ldp(v.dinv, i); }
+    if constexpr (PH == MV_Q_D)    { in.a = ldp(v.r + o, i); in.b = ldp(v.s + o, i); in.c = ldp(v.dinv, i); }
+    if constexpr (PH == MV_XR_H)   { in.a = ldp(v.r + o, i); in.b = ldp_nt(v.x + o, i); in.c = ldp(v.ph + o, i); in.d = ldp(v.y + o, i); in.e = ldp(v.rh + o, i); in.f = ldp(v.qh + o, i); }
+    if constexpr (PH == MV_P_D)    { in.a = ldp(v.p + o, i); in.b = ldp(v.r + o, i); in.c = ldp(v.s + o, i); in.d = ldp(v.dinv, i); }
     return in;
 }
 template <int PH> __device__ __forceinline__ In<PH, double> fetch1(const MultiVecs &v, size_t o, uint32_t i)
@@ -76,11 +88,17 @@ template <int PH> __device__ __forceinline__ In<PH, double> fetch1(const MultiVe
     if constexpr (PH == MV_DOT_QY) { in.a = v.r[o + i]; in.b = v.y[o + i]; }
     if constexpr (PH == MV_XR)     { in.a = v.r[o + i]; in.b = v.x[o + i]; in.c = v.p[o + i]; in.d = v.y[o + i]; in.e = v.rh[o + i]; }
     if constexpr (PH == MV_P)      { in.a = v.p[o + i]; in.b = v.r[o + i]; in.c = v.s[o + i]; }
+    if constexpr (PH == MV_INIT_D) { in.a = v.r[o + i]; in.b = v.s[o + i]; in.c = v.dinv[i]; }
+    if constexpr (PH == MV_Q_D)    { in.a = v.r[o + i]; in.b = v.s[o + i]; in.c = v.dinv[i]; }
+    if constexpr (PH == MV_XR_H)   { in.a = v.r[o + i]; in.b = v.x[o + i]; in.c = v.ph[o + i]; in.d = v.y[o + i]; in.e = v.rh[o + i]; in.f = v.qh[o + i]; }
+    if constexpr (PH == MV_P_D)    { in.a = v.p[o + i]; in.b = v.r[o + i]; in.c = v.s[o + i]; in.d = v.dinv[i]; }
     return in;
 }
 __device__ __forceinline__ double dotT(double x, double y) { return x * y; }
 __device__ __forceinline__ double dotT(pr x, pr y) { return dot2(x, y); }
 __device__ __forceinline__ double scal(double a, double x) { return a * x; }
+__device__ __forceinline__ double had(double d, double x) { return d * x; }                     // dinv o x: one rounding per entry
+__device__ __forceinline__ pr had(pr d, pr x) { return {d.a * x.a, d.b * x.b}; }
 __device__ __forceinline__ void put(double *p, size_t o, uint32_t i, double v) { p[o + i] = v; }
 __device__ __forceinline__ void put(double *p, size_t o, uint32_t i, pr v) { stp(p + o, i, v); }
 __device__ __forceinline__ void put_nt(double *p, size_t o, uint32_t i, double v) { __builtin_nontemporal_store(v, p + o + i); }
@@ -115,6 +133,33 @@ __device__ __forceinline__ void compute(const MultiVecs &v, size_t o, uint32_t i
         pp = axpy(pp, k.c, in.c);
         put(v.p, o, i, pp);
     }
+    if constexpr (PH == MV_INIT_D) {           // MV_INIT ; p^ = dinv o p
+        const T rr = axpy(in.a, -1.0, in.b);
+        put(v.r, o, i, rr); put(v.rh, o, i, rr); put(v.p, o, i, rr);
+        put(v.ph, o, i, had(in.c, rr));
+        acc[0] += dotT(rr, rr);
+    }
+    if constexpr (PH == MV_Q_D) {              // MV_Q ; q^ = dinv o q
+        const T q = axpy(in.a, -k.alpha, in.b);
+        put(v.r, o, i, q);
+        put(v.qh, o, i, had(in.c, q));
+    }
+    if constexpr (PH == MV_XR_H) {             // x = (x + alpha p^) + omega q^ ; r, (r,r), (r#,r) as MV_XR
+        T xx = axpy(in.b, k.alpha, in.c);
+        xx = axpy(xx, k.omega, in.f);
+        put_nt(v.x, o, i, xx);
+        const T rr = axpy(in.a, -k.omega, in.d);
+        put(v.r, o, i, rr);
+        acc[0] += dotT(rr, rr);
+        acc[1] += dotT(in.e, rr);
+    }
+    if constexpr (PH == MV_P_D) {              // MV_P ; p^ = dinv o p
+        T pp = scal(k.beta, in.a);
+        pp = axpy(pp, 1.0, in.b);
+        pp = axpy(pp, k.c, in.c);
+        put(v.p, o, i, pp);
+        put(v.ph, o, i, had(in.d, pp));
+    }
 }
 
 }  // namespace
@@ -124,7 +169,7 @@ __global__ void __launch_bounds__(kBlock) k_multi_vec(MultiVecs v, const MultiSc
 {
     constexpr int ND = mv_dots<PH>::value;
     const int col = blockIdx.y;
-    if (PH != MV_INIT && !S->active[col]) return;      // frozen: workgroup-uniform, before the first vector load
+    if (PH != MV_INIT && PH != MV_INIT_D && !S->active[col]) return;      // frozen: workgroup-uniform, before the first vector load
     const size_t o = (size_t)col * v.stride;
     const uint32_t n = v.n, npair = n >> 1;
     const uint32_t t0 = blockIdx.x * (uint32_t)(kBlock * kMultiTile) + threadIdx.x;
@@ -135,9 +180,9 @@ __global__ void __launch_bounds__(kBlock) k_multi_vec(MultiVecs v, const MultiSc
         if (i < npair) in[u] = fetch<PH>(v, o, 2 * i);
     }
     Coef k{};
-    if constexpr (PH == MV_Q) k.alpha = S->alpha[col];
-    if constexpr (PH == MV_XR) { k.alpha = S->alpha[col]; k.omega = S->omega[col]; }
-    if constexpr (PH == MV_P) { k.beta = S->beta[col]; k.c = -S->beta[col] * S->omega[col]; }
+    if constexpr (PH == MV_Q || PH == MV_Q_D) k.alpha = S->alpha[col];
+    if constexpr (PH == MV_XR || PH == MV_XR_H) { k.alpha = S->alpha[col]; k.omega = S->omega[col]; }
+    if constexpr (PH == MV_P || PH == MV_P_D) { k.beta = S->beta[col]; k.c = -S->beta[col] * S->omega[col]; }
     double acc[ND > 0 ? ND : 1] = {};
 #pragma unroll
     for (int u = 0; u < kMultiTile; ++u) {
@@ -281,6 +326,10 @@ void launch_multi_q(const MultiVecs &v, int nv, MultiScal *S, hipStream_t st) { 
 void launch_multi_dot_qy(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st) { run_multi<MV_DOT_QY>(v, nv, S, part, st); }
 void launch_multi_xr(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st) { run_multi<MV_XR>(v, nv, S, part, st); }
 void launch_multi_p(const MultiVecs &v, int nv, MultiScal *S, hipStream_t st) { run_multi<MV_P>(v, nv, S, nullptr, st); }
+void launch_multi_init_diag(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st) { run_multi<MV_INIT_D>(v, nv, S, part, st); }
+void launch_multi_q_diag(const MultiVecs &v, int nv, MultiScal *S, hipStream_t st) { run_multi<MV_Q_D>(v, nv, S, nullptr, st); }
+void launch_multi_xr_hat(const MultiVecs &v, int nv, MultiScal *S, double *part, hipStream_t st) { run_multi<MV_XR_H>(v, nv, S, part, st); }
+void launch_multi_p_diag(const MultiVecs &v, int nv, MultiScal *S, hipStream_t st) { run_multi<MV_P_D>(v, nv, S, nullptr, st); }
 
 void launch_multi_finish(int phase, int nv, MultiScal *S, const double *part, unsigned nwg, hipStream_t st)
 {

@@ -46,6 +46,14 @@ void precond_apply(bicg_ctx *c, const double *in, double *out)
     launch_bjac_apply(m.planes, m.stride, m.bs, ro ? c->ro_perm : nullptr, ro ? c->ro_inv : nullptr, in, out, c->n_loc, c->sc);
 }
 
+void precond_apply_set(bicg_ctx *c, const double *in, double *out, int nv, const MultiScal *S, int chunk)
+{
+    const Precond &m = c->pc;
+    const bool ro = m.kind == Precond::BLOCK && c->reordered;
+    launch_bjac_apply_set(m.planes, m.stride, m.bs, ro ? c->ro_perm : nullptr, ro ? c->ro_inv : nullptr, in, out, c->stride, c->n_loc, nv, S,
+                          chunk, c->sc);
+}
+
 // src_dev: the caller's d (DIAGONAL) or blocks (BLOCK) on the device, caller's numbering. One launch prepares the result outside
 // the resident array and raises the flag for an entry or block it has to refuse: 1 / d -- through the permutation on a reordered
 // context -- into the context's ax vector (free between any two calls: every solver writes it, a product's output, before it reads

@@ -78,7 +78,7 @@ EXPORTS = [
     "bicg_load_device", "bicg_fetch_device", "bicg_solve_device", "bicg_spmv_device", "bicg_solve_multi_device",
     "bicg_precond_diagonal", "bicg_precond_diagonal_device", "bicg_precond_clear", "bicg_precond_kind", "bicg_csr_diagonal",
     "bicg_precond_block_diagonal", "bicg_precond_block_diagonal_device", "bicg_precond_apply", "bicg_csr_block_diagonal",
-    "bicg_precond_apply_bench",
+    "bicg_precond_apply_bench", "bicg_precond_apply_set_bench",
 ]
 
 _lib = None
@@ -194,6 +194,8 @@ def lib():
         L.bicg_precond_apply.argtypes = [C.c_void_p, _dp, _dp]
         L.bicg_precond_apply_bench.argtypes = [C.c_void_p, C.c_int, _dp]
         L.bicg_precond_apply_bench.restype = C.c_int
+        L.bicg_precond_apply_set_bench.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp]
+        L.bicg_precond_apply_set_bench.restype = C.c_int
         L.bicg_csr_block_diagonal.argtypes = [C.POINTER(CSRMatrix), C.c_int, _dp]
         L.block_jacobi_bicgstab.argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp, C.c_int]
         for fn in (L.bicg_precond_block_diagonal, L.bicg_precond_block_diagonal_device, L.bicg_precond_apply, L.bicg_csr_block_diagonal,
@@ -483,6 +485,14 @@ class Context:
             raise RuntimeError("bicg_precond_apply_bench: the context has no preconditioner (set_diagonal / set_block_diagonal)")
         return ms.value
 
+    def apply_preconditioner_set_bench(self, ncols: int, reps: int, chunk: int = 0) -> float:
+        """ms per set application of the installed block preconditioner on ncols (1..16) columns, one launch each, reps back to back on
+        the device (bicg_precond_apply_set_bench); chunk: columns a workgroup walks, 4 / 8 / 16, 0 = the library's choice"""
+        ms = C.c_double(0.0)
+        if lib().bicg_precond_apply_set_bench(self.h, ncols, chunk, reps, C.byref(ms)) != 0:
+            raise RuntimeError("bicg_precond_apply_set_bench: no block preconditioner (set_block_diagonal), or ncols outside 1..16")
+        return ms.value
+
     def clear_preconditioner(self) -> int:
         """drop the preconditioner, of either kind, and its device array (bicg_precond_clear)"""
         return int(lib().bicg_precond_clear(self.h))
@@ -569,8 +579,9 @@ class Context:
         return dict(k=np.array(self._multi_k, dtype=np.int64), x=x, r=r, results=results, rc=rc)
 
     def solve_multi(self, B, X0=None, method: str = "bicgstab", nrhs=None, **kw):
-        """Plain BiCGStab on the rows of B [nrhs][n] as independent right-hand sides of the resident matrix, 16 columns per pass
-        over the matrix (bicg_solve_multi): dict(k [nrhs] int array, x [nrhs][n], r [nrhs][n], results [nrhs] of Result, rc = the
+        """BiCGStab on the rows of B [nrhs][n] as independent right-hand sides of the resident matrix, 16 columns per pass over the
+        matrix (bicg_solve_multi). method: "bicgstab", or right-preconditioned "bicgstab_diag" / "bicgstab_block" on a context that
+        holds that preconditioner (set_diagonal / set_block_diagonal; otherwise rc = -2). Returns dict(k [nrhs] int array, x [nrhs][n], r [nrhs][n], results [nrhs] of Result, rc = the
         call's return value: the largest k, or the negative code of a refused call -- x and r are then X0 and B). Collective
         across ranks (rc = -1: the ranks passed different arguments); nrhs: the number of columns where B cannot tell -- a rank
         without rows (n = 0) passes it with empty arrays. B / X0 as CUDA float64 torch tensors: the device form
