@@ -720,6 +720,26 @@ int bicg_sell_plan_digest(const CSR_Matrix *diag, const CSR_Matrix *offd_renumbe
  *   blocks), 2 entries of the list, 3 reads the offd block, 4 exchange inside, 5 first partial slot, 6 runs after the halo has
  *   landed}, in launch order; rows from plan[9] on are zero. Returns 0, 1 for a null array or an unknown transport. */
 int bicg_spmv_launch_plan(const unsigned int shape[15], const int call[5], unsigned int plan[10], unsigned int steps[28]);
+/* Who closes a dot group (host only, what every solver asks when it opens a group): what the producer's
+ * reduction descriptor says and the ordered operations that turn the group's sums into applied scalars, as numbers a test can
+ * pin. Needs no context and no device; reads no environment.
+ * shape = {0 transport (0 one rank, 1 peer-to-peer, 2 hosted), 1 the hosted collectives run in stream order, 2 two streams
+ *   (BICG_OVERLAP), 3 peer-to-peer: the producer's last workgroup may collect and apply, 4 tail finish switched on, 5 iterations
+ *   are replayed from a captured graph, 6 hand-over switched on and possible on this matrix}.
+ * call = {0 regime (0 tickets / tail finish, 1 consumer-side finish, 2 hand-over), 1 sums, 2 their offset in Scal::red, 3 phase,
+ *   4 one rank: the producer applies the recurrence, 5 event (0 a group that closes at once, 1 one deferred across the next
+ *   product, 2 the host or a product needs the open group's scalars before a consumer came, 3 the consuming kernel's launch, 4 a
+ *   producer that neither opens nor closes), 6 the group open when the call is made (0 none, 1 open, 2 deferred and not yet
+ *   staged, 3 staged by a product), 7 the call comes from a product}.
+ * plan = {0 error (0 none, 1 a group produced while one is open, 2 a product with dots asked to stage a deferred group, 3 a
+ *   hand-over consumer without a group), 1-3 the producer's Reduce: wave, hand, apply_now, 4 its p2p.n_collect, 5 it carries a new
+ *   tail tag, 6 it publishes to the peers' mailboxes, 7 the group rides across the next product, 8 steps}.
+ * steps = 7 rows of {0 operation (0 nothing: the producer's last workgroup did it, 1 stand-alone finish, 2 all-reduce, 3 k_apply,
+ *   4 k_apply_p2p, 5 event recorded on the stream, 6 the stream waits for the event recorded last, 7 staged by the next product's
+ *   first launch, 8 finished by the consuming kernel), 1 when (0 at close, 1 behind the next product's halo start, 2 after that
+ *   product, 3 in the consumer), 2 stream (0 compute, 1 communication), 3 FIN_* roles, 4 sums, 5 offset, 6 phase}, in order; rows
+ *   from plan[8] on are zero. Returns 0, 1 for a null array or an entry outside its range. */
+int bicg_dot_group_plan(const int shape[7], const int call[8], int plan[9], int steps[49]);
 
 /* Bandwidth-reducing renumbering of a diag block (host only, what bicg_create does under
  * BICG_PLAN="reorder=1|2"). Reverse Cuthill-McKee on the symmetrised pattern (entry (i, j) makes i and j neighbours whichever of

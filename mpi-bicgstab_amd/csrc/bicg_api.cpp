@@ -192,7 +192,7 @@ int bicg_spmv(bicg_ctx *c, const double *x, double *y)
     x = host_in(c, x); y = host_out(c, y);
     vec_upload(c, c->v.p, c->stride, x, 1, true);
     c->time_kernels = false;
-    spmv(c, c->v.p, c->v.s, 0, nullptr, c->red(0, PH_NONE));
+    spmv(c, c->v.p, c->v.s, 0, nullptr, c->dots.no_dots());
     vec_download(c, y, c->v.s, c->stride, 1, true);
     if (c->p2p) fetch_scal(c);      // also reports a peer that never delivered its halo values
     else BICG_HIP(hipStreamSynchronize(c->sc));
@@ -207,7 +207,7 @@ int bicg_spmv_device(bicg_ctx *c, const double *x_d, double *y_d, void *stream)
     cross_begin(c, (hipStream_t)stream);
     cross_in(c, c->v.p, x_d, nullptr, nullptr, c->stride, c->n_loc, 1);
     c->time_kernels = false;
-    spmv(c, c->v.p, c->v.s, 0, nullptr, c->red(0, PH_NONE));
+    spmv(c, c->v.p, c->v.s, 0, nullptr, c->dots.no_dots());
     cross_out(c, y_d, c->v.s, nullptr, nullptr, c->stride, c->n_loc, 1);
     cross_end(c, (hipStream_t)stream);
     if (c->p2p) fetch_scal(c);      // as bicg_spmv: reports a peer that never delivered its halo values; otherwise no host wait
@@ -221,8 +221,8 @@ double bicg_dot(bicg_ctx *c, const double *x, const double *y)
     if (c->phantom) { x = host_in(c, x); y = x; }
     vec_upload(c, c->v.p, c->stride, x, 1, true);
     vec_upload(c, c->v.s, c->stride, y, 1, true);
-    launch_dot(c->v.p, c->v.s, c->n_loc, c->S, c->red(0, PH_NONE, true, 1), c->sc);
-    group_now(c, 1, PH_NONE);
+    launch_dot(c->v.p, c->v.s, c->n_loc, c->S, c->dots.open(1, PH_NONE), c->sc);
+    c->dots.close();
     fetch_scal(c);
     return c->hS->red[0];
 }
@@ -240,8 +240,8 @@ int bicg_shifted_residuals(bicg_ctx *c, const double *x_loc_set, const double *b
     vec_upload(c, c->v.b, c->stride, b_loc, 1, true);
     BICG_HIP(hipMemsetAsync(c->v.t, 0, sizeof(double) * c->stride, c->sc));
     c->time_kernels = false;
-    launch_dot(c->v.b, c->v.b, c->n_loc, c->S, c->red(0, PH_NONE, true, 1), c->sc);
-    group_now(c, 1, PH_NONE);
+    launch_dot(c->v.b, c->v.b, c->n_loc, c->S, c->dots.open(1, PH_NONE), c->sc);
+    c->dots.close();
     fetch_scal(c);
     const double bb = c->hS->red[0];
     if (c->spmm_ok && !plan_off("spmm")) {
@@ -272,10 +272,10 @@ int bicg_shifted_residuals(bicg_ctx *c, const double *x_loc_set, const double *b
     for (int j = 0; j < nsig; ++j) {
         vec_upload(c, c->v.p, c->stride, x_loc_set + (size_t)j * n, 1, true);
         c->cur_shift = sigma[j]; c->cur_has_shift = true;
-        spmv(c, c->v.p, c->v.ax, 0, nullptr, c->red(0, PH_NONE));
+        spmv(c, c->v.p, c->v.ax, 0, nullptr, c->dots.no_dots());
         c->cur_has_shift = false; c->cur_shift = 0.0;
-        launch_drift(w, Launch{c->S, Finish{}, c->sc}, c->red(0, PH_NONE, true, 2));
-        group_now(c, 2, PH_NONE);
+        launch_drift(w, Launch{c->S, Finish{}, c->sc}, c->dots.open(2, PH_NONE));
+        c->dots.close();
         fetch_scal(c);
         relres_out[j] = bb > 0.0 ? sqrt(c->hS->red[0] / bb) : sqrt(c->hS->red[0]);
     }
@@ -325,11 +325,11 @@ int bicg_spmv_bench(bicg_ctx *c, int reps, double *ms_per_spmv)
     BICG_HIP(hipMemcpyAsync(c->v.p, ones.data(), sizeof(double) * c->n_loc, hipMemcpyHostToDevice, c->sc));
     BICG_HIP(hipStreamSynchronize(c->sc));
     c->time_kernels = false;
-    for (int i = 0; i < 3; ++i) spmv(c, c->v.p, c->v.s, 0, nullptr, c->red(0, PH_NONE));
+    for (int i = 0; i < 3; ++i) spmv(c, c->v.p, c->v.s, 0, nullptr, c->dots.no_dots());
     hipEvent_t a, b;
     BICG_HIP(hipEventCreate(&a)); BICG_HIP(hipEventCreate(&b));
     BICG_HIP(hipEventRecord(a, c->sc));
-    for (int i = 0; i < reps; ++i) spmv(c, c->v.p, c->v.s, 0, nullptr, c->red(0, PH_NONE));
+    for (int i = 0; i < reps; ++i) spmv(c, c->v.p, c->v.s, 0, nullptr, c->dots.no_dots());
     BICG_HIP(hipEventRecord(b, c->sc));
     BICG_HIP(hipEventSynchronize(b));
     float ms = 0.f;
@@ -442,7 +442,7 @@ unsigned int bicg_ctx_flags(bicg_ctx *c)
     if (c->constant_entries) f |= BICG_FLAG_CONSTANT;
     if (c->reordered) f |= BICG_FLAG_REORDERED;
     if (plain_handover(c)) f |= BICG_FLAG_HANDOVER;
-    if (c->tail_finish && !c->p2p && c->tail_tab && c->graph_mode != 1) f |= BICG_FLAG_TAIL_FINISH;
+    if (c->dots.tail_available()) f |= BICG_FLAG_TAIL_FINISH;
     return f;
 }
 

@@ -384,27 +384,7 @@ static void ctx_state(bicg_ctx *c, Comm *comm, uint32_t ngroups)
     for (int i = 0; i < 12; ++i) *slots[i] = base + (size_t)i * c->stride;
     c->v.n = c->n_loc;
 
-    c->nslots = std::max<unsigned>(ngroups + c->nblk, kMaxGrid) + 64;
-    c->partial = c->own.alloc<double>((size_t)c->nslots * kPartialStride);
-    c->shard_tot = c->own.alloc<double>((size_t)kShards * kPartialStride);
-    c->counter = c->own.alloc<unsigned>((kShards + 1) * kCounterStride);
-    BICG_HIP(hipMemset(c->counter, 0, sizeof(unsigned) * (kShards + 1) * kCounterStride));
-    c->tail_tab = c->own.alloc<llword>((size_t)c->nslots * kTailStride);
-    BICG_HIP(hipMemset(c->tail_tab, 0, sizeof(llword) * (size_t)c->nslots * kTailStride));
-    c->tail_shard = c->own.alloc<llword>((size_t)kShards * kRedSlots * 2);
-    BICG_HIP(hipMemset(c->tail_shard, 0, sizeof(llword) * kShards * kRedSlots * 2));
-    if (const char *sv = getenv("BICG_TAIL_FINISH")) c->tail_finish = atoi(sv) != 0;      // 0: every ticket-mode group closes by arrival tickets
-    c->hand_shard = c->own.alloc<llword>((size_t)2 * kRedSlots * kShards * 2);
-    BICG_HIP(hipMemset(c->hand_shard, 0, sizeof(llword) * 2 * kRedSlots * kShards * 2));
-    c->Sbuf = c->own.alloc<Scal>(2);
-    BICG_HIP(hipMemset(c->Sbuf, 0, 2 * sizeof(Scal)));
-    c->S = c->Sbuf;
-    for (int i = 0; i < 2; ++i) {
-        c->wpart[i] = c->own.alloc<double>((size_t)c->nslots * (kBlock / 64) * kPartialStride);
-        BICG_HIP(hipMemset(c->wpart[i], 0, sizeof(double) * (size_t)c->nslots * (kBlock / 64) * kPartialStride));
-    }
-    c->shard_ll = c->own.alloc<llword>((size_t)2 * kShardLL * kRedSlots * 2);
-    BICG_HIP(hipMemset(c->shard_ll, 0, sizeof(llword) * 2 * kShardLL * kRedSlots * 2));
+    c->dots.init(c, std::max<unsigned>(ngroups + c->nblk, kMaxGrid) + 64);      // the dot groups' memory, events and the two scalar blocks
     c->alarm = c->own.alloc<int>(1);
     BICG_HIP(hipMemset(c->alarm, 0, sizeof(int)));
     c->refresh_flag = c->own.alloc<int>(1);
@@ -425,8 +405,6 @@ static void ctx_streams(bicg_ctx *c, int P)
     for (int i = 0; i < kEvRing; ++i) {
         BICG_HIP(hipEventCreateWithFlags(&c->ev_pack[i], hipEventDisableTiming));
         BICG_HIP(hipEventCreateWithFlags(&c->ev_halo[i], hipEventDisableTiming));
-        BICG_HIP(hipEventCreateWithFlags(&c->ev_dots[i], hipEventDisableTiming));
-        BICG_HIP(hipEventCreateWithFlags(&c->ev_red[i], hipEventDisableTiming));
     }
     BICG_HIP(hipDeviceSynchronize());       // uploads and memsets above used the null stream
 }
@@ -484,7 +462,7 @@ static void ctx_read_switches(bicg_ctx *c)
     if (const char *sv = knob_x("BICG_SELL_XCD")) c->sell_xcd = atoi(sv);
     if (const char *sv = test_tok("force-comm")) c->force_comm = atoi(sv) != 0;
     if (const char *sv = plan_tok("reorder")) c->reorder_mode = atoi(sv);
-    c->handover = !plan_off("handover");
+    c->dots.handover = !plan_off("handover");
 }
 
 // what the halo plan leaves on the host for the later stages (uploads, the persistent plan, the transport)
@@ -501,7 +479,7 @@ struct HaloHost {
 static void ctx_finish(bicg_ctx *c, Comm *comm, uint32_t ngroups, const CSR_Matrix *diag, const HaloHost *host, PlanTrace &trace)
 {
     ctx_state(c, comm, ngroups);
-    if (const char *sv = test_tok("spin-ticks")) c->spin_ticks = strtoull(sv, nullptr, 10);
+    if (const char *sv = test_tok("spin-ticks")) c->dots.spin_ticks = strtoull(sv, nullptr, 10);
     // Round 4: with the products alternating direction and reading no column index in uniform slices, a big block is faster
     // as two plain products + two element-wise kernels (Transport-shaped, one GPU: 139.0 vs 152.0 us per pipelined iteration;
     // profiles/NOTES.md): the fused two-launch form stays what it was built for -- the latency-bound ranks.
@@ -763,8 +741,8 @@ static void p2p_transport(bicg_ctx *c, Comm *comm, const SellPlan &plan, HaloHos
     // in-kernel collect needs the HEAVY kernel instantiations (occupancy 5 instead of 8 waves per SIMD,
     // ~3 % per SpMV): worth it unless the local problem is so large that 3 % exceeds the ~10 us per
     // iteration the separate apply kernels cost
-    c->inline_apply = c->nnz_d < 40000000u;
-    if (const char *sv = knob_x("BICG_P2P_INLINE_APPLY")) c->inline_apply = atoi(sv) != 0;
+    c->dots.inline_apply = c->nnz_d < 40000000u;
+    if (const char *sv = knob_x("BICG_P2P_INLINE_APPLY")) c->dots.inline_apply = atoi(sv) != 0;
     if (!(c->p2p && !c->single())) { c->p2p = nullptr; return; }
     c->halo_ring = (llword *)c->p2p->alloc(sizeof(llword) * 2 * (size_t)kHaloRing * c->halo);
     std::vector<void *> rings;
@@ -1149,7 +1127,7 @@ void bicg_destroy(bicg_ctx *c)
     if (c->hS) (void)hipHostFree(c->hS);
     if (c->h_alarm) (void)hipHostFree(c->h_alarm);
     for (int i = 0; i < kEvRing; ++i) {
-        for (hipEvent_t e : {c->ev_pack[i], c->ev_halo[i], c->ev_dots[i], c->ev_red[i]})
+        for (hipEvent_t e : {c->ev_pack[i], c->ev_halo[i], c->dots.ev_dots[i], c->dots.ev_red[i]})
             if (e) (void)hipEventDestroy(e);      // a context that failed early in bicg_create has none
     }
     for (auto &e : c->tev) (void)hipEventDestroy(e);

@@ -1,6 +1,7 @@
 // bicg_host.h -- what the host-side translation units of the library share: the context of a rank (struct bicg_ctx), the
 // device-memory helpers and their owner (dev_alloc / dev_free, struct DevOwner), section timing, and the prototypes of the functions that cross file boundaries.
-//   bicg_solver.cpp   dot groups, the distributed SpMV (its launch plan: bicg_spmv_plan.cpp, host only), the four iterations of reference src/solver.c, run_begin / iterate / end
+//   bicg_dots.cpp     the dot groups (struct DotGroups): one owner, open / close, the executor of dot_group_plan (bicg_dot_plan.cpp, host only)
+//   bicg_solver.cpp   the distributed SpMV (its launch plan: bicg_spmv_plan.cpp, host only), the four iterations of reference src/solver.c, run_begin / iterate / end
 //   bicg_shifted.cpp  the shifted family (src/shifted_solver.c, src/shifted_switching_solver.c) and its section prints
 //   bicg_multi.cpp    bicg_solve_multi: plain BiCGStab on up to kSpmmCols right-hand sides per pass over the matrix
 //   bicg_create.cpp   bicg_create / bicg_create_device_csr: halo plan, upload of the diag block's plan (made by bicg_sell_plan.cpp,
@@ -120,7 +121,7 @@ struct Precond {
 // What the host code needs to know about a solver method (the enum of include/bicgstab_hip.h), in one place
 struct MethodInfo {
     int nvec;                   // work vectors counted for the matrix-stream policy (run_begin)
-    bool pipelined;             // dot groups deferred across a product: consumer-side finish (bicg_ctx::wave_mode)
+    bool pipelined;             // dot groups deferred across a product: consumer-side finish (DotGroups::wave_mode)
     Precond::Kind precond;      // the preconditioner the method needs on the context
     bool persist;               // may take the persistent launch at all (run_iterate decides per context)
 };
@@ -135,6 +136,85 @@ constexpr MethodInfo kMethod[] = {
 constexpr int kMethods = (int)(sizeof kMethod / sizeof kMethod[0]);
 static_assert(BICG_BICGSTAB == 0 && BICG_BICGSTAB_BLOCK == kMethods - 1, "kMethod follows the method enum");
 inline Precond::Kind precond_kind_of(int method) { return method >= 0 && method < kMethods ? kMethod[method].precond : Precond::NONE; }
+
+// The dot groups of a context (bicg_dots.cpp): every buffer, counter, event and piece of bookkeeping of the
+// three regimes -- tickets / tail finish, consumer-side finish (wave), hand-over -- and the one interface through which the solvers
+// open and close a group. WHICH operations close a group is dot_group_plan's decision (bicg_plan.h, host only, pinned by the CPU
+// suite); the methods below execute that plan and keep the sequence numbers, on which the ranks agree only because every rank
+// runs the same host code. A group is opened once -- n, offset, phase, now or deferred -- and close() takes no argument.
+struct bicg_ctx;
+struct DotGroups {
+    bicg_ctx *c = nullptr;
+    // ---- device memory (init; the context's DevOwner frees it) and switches
+    unsigned nslots = 0;
+    double *partial = nullptr, *shard_tot = nullptr;      // ticket groups: one partial per workgroup, shard totals
+    unsigned *counter = nullptr;                          // ... arrival tickets
+    llword *tail_tab = nullptr, *tail_shard = nullptr;    // tail finish of ticket groups (struct Reduce): LL table + shard totals
+    bool tail_finish = true;                              // BICG_TAIL_FINISH=0: arrival tickets
+    double *wpart[2] = {nullptr, nullptr};                // wave groups: per-wavefront partial sums, alternating between groups
+    llword *shard_ll = nullptr;                           // 2 x [kShards][kRedSlots][2], alternating like wpart
+    unsigned long long spin_ticks = 2000;                 // 20 us before a workgroup sums a missing shard itself (BICG_TEST="spin-ticks=n")
+    // hand-over of plain BiCGStab's three groups (RED_HAND): two shard-total tables [kRedSlots][kShards][2] that alternate group by
+    // group (FPlainXR reads one group's totals while its last workgroups write the next group's). BICG_PLAN="handover=0": off
+    bool handover = true;
+    llword *hand_shard = nullptr;
+    bool inline_apply = true;                             // peer-to-peer, BICG_P2P_INLINE_APPLY=0: always the separate apply kernel
+    hipEvent_t ev_dots[kEvRing] = {}, ev_red[kEvRing] = {};
+    unsigned i_dots = 0, i_red = 0;
+    // ---- bookkeeping
+    bool wave_mode = false;      // this solve's groups are wave groups (reset); false: tickets
+    int cur = 0;                 // the current scalar block: c->S == c->Sbuf + cur
+    unsigned grp_seq = 0, tail_seq = 0;
+    struct Group {               // the open ticket or wave group
+        bool active = false;     // opened, not yet closed / consumed
+        bool staged = false;     // a product's launch has already summed the shards / pushed the sums to the peers
+        unsigned seq = 0, mail_seq = 0, nparts = 0;
+        int buf = 0;
+        DotCall call;            // what open() was told
+        DotPlan plan;            // ... and what dot_group_plan made of it
+    } grp;
+    struct Hand {
+        unsigned seq = 0, nsh = 0;   // tag of the open group (0: none), shard totals its producer leaves
+        int n = 0, phase = 0, buf = 0;
+    } hand;
+    struct Pending {             // a closed group whose remaining steps ride on the next product
+        bool on = false, joined = false;
+        DotPlan plan;
+        hipEvent_t ev = nullptr;
+        unsigned seq = 0;        // its mailbox number (peer-to-peer)
+    } pend;
+
+    void init(bicg_ctx *ctx, unsigned slots);      // device memory (zeroed), events, switches
+    // a solve or a stand-alone call begins: regime, no group open, fresh arrival tickets, and the current scalar block (both: and the
+    // idle one) set to *block (null: zeroed)
+    void reset(bool wave, const Scal *block = nullptr, bool both = false);
+    DotShape shape() const;                        // what the context tells dot_group_plan (handover: switch and tables only)
+    DotShape shp;                                  // ... as of the last reset (solve_shape)
+    bool tail_available() const { return dot_tail_available(shape()); }
+    void next_block();                             // everything enqueued from now on reads the other scalar block
+    // open a group in the solve's regime (event: DOT_NOW / DOT_DEFER) and return its producer's Reduce; nwg: the producer's
+    // workgroups (0: a product, which reports them through producer_grid)
+    Reduce open(int n, int phase, int event = DOT_NOW, int off = 0, unsigned nwg = 0, bool by_product = false);
+    Reduce open_hand(int n, int phase, unsigned nwg = 0);
+    Reduce contribute(int off, bool apply_single); // a producer that neither opens nor closes (CA-BiCGStab's first of two)
+    Reduce no_dots() { return contribute(0, true); }      // a product without dots
+    void close();                                  // the plan's "at close" steps
+    bool is_open() const { return grp.active && grp.plan.wave; }      // a wave group is open (a ticket group is closed by the call that follows its producer)
+    void force(bool by_product = false);           // the host or a product needs the open wave group's scalars now
+    Launch consume();                              // the launch descriptor of a kernel that finishes the open wave group (if any)
+    Launch consume_hand();
+    // spmv(): the open wave group as the product's first launch sees it; what its launches publish; the two points of a product
+    Finish before_product(bool has_dots);
+    void producer_grid(const Reduce &red, unsigned expected, unsigned hand_nsh, bool sets_nparts);
+    void behind_halo();
+    void after_product();
+    void flush();                                  // a deferred group that no product picked up
+private:
+    const DotShape &solve_shape();
+    Reduce ticket(const DotPlan &p, int off, int phase);
+    Finish desc(int roles) const;
+    void run(const DotPlan &plan, int when, unsigned mail_seq = 0);
+};
 
 constexpr unsigned kWaitCap = 4096;      // samples per row of PersistArgs::waitlog
 struct bicg_ctx {
@@ -208,14 +288,12 @@ struct bicg_ctx {
     std::vector<void *> ring_mapped;
     unsigned halo_seq = 0;          // exchanges started (sequence number of the last one)
     int halo_unsynced = 0;          // exchanges since the last all-reduce or barrier (flow control)
-    unsigned pend_seq = 0;
     bool comm_failed = false;       // a peer-to-peer wait timed out (BICG_P2P_SOFT_FAIL)
     bool soft_fail = false;         // ... report it through comm_failed instead of ending the program (drop-in fallback)
     // Exchange folded into the SpMV launch (HaloLL): possible when every halo-touching row is on the
     // sliced-ELL path. One launch covers push + interior + halo-touching groups (listed in that order).
     bool ll_fused = false;
     uint32_t *glist_ll = nullptr;
-    bool inline_apply = true;       // BICG_P2P_INLINE_APPLY=0: always use the separate apply kernel
     int fault_after = 0;            // BICG_TEST="p2p-fault-after=n" (tests): from the n-th exchange on this rank sends nothing
 
     Precond pc;                     // the one preconditioner of the context (bicg_precond.cpp)
@@ -223,19 +301,10 @@ struct bicg_ctx {
     // vectors and scalars
     double *slab = nullptr;
     Vecs v{};
-    Scal *S = nullptr;           // the scalar block kernels enqueued from now on read (= Sbuf + cur)
+    Scal *S = nullptr;           // the scalar block kernels enqueued from now on read (= Sbuf + dots.cur; DotGroups::next_block)
     Scal *Sbuf = nullptr;        // two blocks: a kernel that finishes a dot group reads one and writes the other
-    int cur = 0;
     Scal *hS = nullptr;          // pinned mirror
-    // consumer-side finish of dot groups (struct Finish, bicg_device.h): the four solvers of src/solver.c
-    struct Group {
-        bool active = false;     // produced, not yet consumed
-        bool deferred = false;   // may ride across the next SpMV (pipelined variants, src/solver.c:363-367)
-        bool staged = false;     // an SpMV launch has already summed the shards / pushed the sums to the peers
-        unsigned seq = 0, mail_seq = 0, nparts = 0;
-        int n = 0, off = 0, phase = 0, buf = 0;
-    } grp;
-    bool wave_mode = false;      // this call uses consumer-side finish (run_begin); false: ticket reductions
+    DotGroups dots;              // the dot groups: their buffers, counters, events and who closes them (bicg_dots.cpp)
     bool spmm_ok = false;        // spmm_possible() on every rank (the SpMM exchanges the halos of all its vectors at once)
     bool fuse_plan_ok = false;   // every row on the sliced-ELL path and one launch per SpMV -- ON EVERY RANK (the fused and the
                                  // separate flow exchange their dot groups differently: the choice is collective)
@@ -258,43 +327,17 @@ struct bicg_ctx {
     unsigned persist_seq = 0;    // LL tags used so far (dot tables)
     unsigned persist_vseq = 0;   // ... by the pipelined kernel's vector images
     unsigned wg_cap = 0;         // ranks sharing this GPU (tests): workgroups per launch that may wait for another rank
-    double *wpart[2] = {nullptr, nullptr};   // per-wavefront partial sums, alternating between groups
-    llword *shard_ll = nullptr;  // 2 x [kShards][kRedSlots][2], alternating like wpart
     int *alarm = nullptr, *h_alarm = nullptr;
-    unsigned grp_seq = 0;
-    unsigned long long spin_ticks = 2000;   // 20 us before a workgroup sums a missing shard itself (BICG_TEST="spin-ticks=n")
-    double *partial = nullptr, *shard_tot = nullptr;
-    unsigned *counter = nullptr;
-    // tail finish of ticket-mode dot groups (struct Reduce): LL table + shard totals; BICG_TAIL_FINISH=0: arrival tickets
-    llword *tail_tab = nullptr, *tail_shard = nullptr;
-    mutable unsigned tail_seq = 0;
-    bool tail_finish = true;
-    // hand-over of plain BiCGStab's three dot groups (RED_HAND): the producer's tail finish stops at the shard totals, the kernel
-    // that consumes the scalars adds them and applies the recurrence. Two shard-total tables [kRedSlots][kShards][2] that alternate
-    // group by group (FPlainXR reads one group's totals while its last workgroups write the next group's), and the scalar blocks
-    // alternate as they do for the pipelined solvers (Sbuf / cur). BICG_PLAN="handover=0": the producer finishes the group itself.
-    bool handover = true;
-    llword *hand_shard = nullptr;
-    struct Hand {
-        unsigned seq = 0, nsh = 0;   // tag of the open group (0: none), shard totals its producer leaves
-        int n = 0, phase = 0, buf = 0;
-    } hand;
-    unsigned nslots = 0;
     double *trace = nullptr;     // 4 * trace_cap
     int trace_cap = 0;
     int last_iters = 0;
 
     hipStream_t sc = nullptr, sm = nullptr;   // compute, communication
-    hipEvent_t ev_pack[kEvRing] = {}, ev_halo[kEvRing] = {}, ev_dots[kEvRing] = {}, ev_red[kEvRing] = {};
-    unsigned i_pack = 0, i_halo = 0, i_dots = 0, i_red = 0;
+    hipEvent_t ev_pack[kEvRing] = {}, ev_halo[kEvRing] = {};
+    unsigned i_pack = 0, i_halo = 0;
     // the *_device entry points (cross_begin / cross_end below): [0] recorded on the caller's stream, the compute stream waits for
     // it; [1] recorded on the compute stream, the caller's stream waits for it. Timing disabled; created by the first such call
     hipEvent_t cross_ev[2] = {nullptr, nullptr};
-
-    // deferred dot group (pipelined variant: all-reduce overlaps the next SpMV)
-    bool pend = false;
-    int pend_n = 0, pend_phase = 0, pend_off = 0;
-    hipEvent_t pend_ev = nullptr;
 
     // shifted solver (bicg_solve_shifted): per-shift scalar state and the two vector sets
     double *sw_buf = nullptr;        // seed-switching variants: archives (doubles) followed by the flag arrays
@@ -389,29 +432,6 @@ struct bicg_ctx {
     hipGraphExec_t graph_exec[kMethods] = {};
     int graph_warm[kMethods] = {};       // eager iterations done since the context was created
     bool graph_nt[kMethods] = {};
-    // now_n > 0: the group is closed by group_now(now_n, phase) right after this producer (not
-    // deferred); with the peer-to-peer transport the producer's finishing workgroup then collects
-    // and applies it in-kernel and group_now launches nothing.
-    mutable bool open_inline = false;
-    Reduce red(int off, int phase, bool apply_single = true, int now_n = 0) const
-    {
-        Reduce r{};
-        r.partial = partial; r.shard_tot = shard_tot; r.counter = counter; r.expected = 0; r.slot_base = 0;
-        r.red_off = off; r.phase = phase;
-        r.apply_now = (single() && apply_single) ? 1 : 0;
-        r.p2p = P2pRed{};
-        r.tail_tab = tail_tab; r.tail_shard = tail_shard;
-        // (not under hipGraph replay: a captured launch would meet its own earlier words under the same tag)
-        r.tail_seq = (tail_finish && !p2p && tail_tab && graph_mode != 1) ? ++tail_seq : 0u;
-        if (p2p) {
-            r.p2p = p2p->red_desc(p2p->red_seq);   // the group being produced; closed by group_now/defer
-            if (apply_single && now_n > 0 && inline_apply) {
-                r.apply_now = 1; r.p2p.n_collect = now_n;
-                open_inline = true;
-            }
-        }
-        return r;
-    }
 };
 
 // contexts alive in this process: a context holds pointers into its communicator (transport, peer-to-peer state),
@@ -508,22 +528,13 @@ struct Section {       // the enclosed launches belong to `label`; afterwards th
 };
 
 // ---- dot groups, products, iterations (bicg_solver.cpp)
-Reduce grp_produce(bicg_ctx *c, int off, int n, int phase, unsigned nwg = 0);
-Finish grp_desc(bicg_ctx *c, int roles);
-void grp_close(bicg_ctx *c, bool local_only = false);
-Launch grp_consume(bicg_ctx *c);
-Finish grp_for_spmv(bicg_ctx *c);
-void group_enqueue(bicg_ctx *c, int n, int phase, hipEvent_t after);
-void group_now(bicg_ctx *c, int n, int phase);
-void group_defer(bicg_ctx *c, int n, int phase);
-void group_flush(bicg_ctx *c);
 bool stencil_product(const bicg_ctx *c);
 bool plain_handover(const bicg_ctx *c);      // plain BiCGStab on this context hands its dot groups over to the consuming kernels
 bool hosted(const bicg_ctx *c);      // several ranks whose collectives the host enqueues (RCCL / host transports)
 void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Reduce red, Finish fin = Finish{}, int epi = 0,
           Scal *S = nullptr);
-void spmv_grp(bicg_ctx *c, double *xin, double *yout, int ndot = 0, const double *u = nullptr, int phase = PH_NONE);
-void spmv_epi(bicg_ctx *c, double *xin, double *yout, int epi, int nd, int phase);
+void spmv_grp(bicg_ctx *c, double *xin, double *yout, int ndot = 0, const double *u = nullptr, int phase = PH_NONE, int event = DOT_NOW);
+void spmv_epi(bicg_ctx *c, double *xin, double *yout, int epi, int nd, int phase, int event);
 void halo_only(bicg_ctx *c, double *xin);
 void halo_set(bicg_ctx *c, double *in, int nvec);      // ... of nvec vectors c->stride apart in ONE transport exchange
 void spmm_pass(bicg_ctx *c, int nvec, const double *sigma_host, bool with_b, bool sigma_staged = false, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
@@ -532,6 +543,8 @@ void spmm_stage_sigma(bicg_ctx *c, int nvec, const double *sigma_host);
 bool spmm_possible(const bicg_ctx *c);
 void spmm_buffers(bicg_ctx *c);
 void scal_reset(bicg_ctx *c);
+Scal scal_block(const bicg_ctx *c, const bicg_options &o);      // the scalar block a solve starts from
+void persist_args(bicg_ctx *c, PersistArgs &a, unsigned groups, unsigned fixed_iters);      // what every persistent launch is told
 void fetch_scal(bicg_ctx *c);
 void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in);
 int run_iterate(bicg_ctx *c, int nsteps);

@@ -75,7 +75,7 @@ void multi_product(bicg_ctx *c, bool spmm, double *in, double *out, int nv, cons
         return;
     }
     for (int j = 0; j < nv; ++j)
-        if (live[j]) spmv(c, in + (size_t)j * st, out + (size_t)j * st, 0, nullptr, c->red(0, PH_NONE));
+        if (live[j]) spmv(c, in + (size_t)j * st, out + (size_t)j * st, 0, nullptr, c->dots.no_dots());
 }
 
 void fetch_multi(bicg_ctx *c, MultiScal *h)

@@ -1,6 +1,6 @@
 // bicg_plan.h -- the plans that are made on the host without a device: the persistent iteration's (persist_plan_host,
 // bicg_plan.cpp), the sliced-ELL plan of the diag block (sell_plan_host, bicg_sell_plan.cpp), the launch plan of a product
-// (spmv_plan, bicg_spmv_plan.cpp) and the renumbering of a badly
+// (spmv_plan, bicg_spmv_plan.cpp), who closes a dot group (dot_group_plan, bicg_dot_plan.cpp) and the renumbering of a badly
 // numbered diag block (reorder_rcm / permute_block, bicg_reorder.cpp). Plain data: device vector
 // types appear as element types only, nothing here calls the HIP runtime or reads the environment.
 #pragma once
@@ -165,6 +165,60 @@ SpmvPlan spmv_plan(const SpmvShape &s, const SpmvCall &k);
 const char *spmv_plan_error(int error);   // the message spmv() ends the program with
 // bicg_spmv_launch_plan (include/bicgstab_hip.h section 5): lengths of its arrays
 constexpr int kSpmvShapeLen = 15, kSpmvCallLen = 5, kSpmvPlanLen = 10, kSpmvStepLen = 7;
+
+// Who closes a dot group (dot_group_plan, bicg_dot_plan.cpp): what the producer's Reduce says and the ordered
+// operations that turn the group's sums into scalars, as a pure function of what the context says (DotShape) and what one call
+// says (DotCall), so that the CPU suite pins it (tests/test_dot_group_plan.py). DotGroups (bicg_host.h, bicg_dots.cpp) only
+// executes it. No HIP call, no environment, no heap, no static state. The transports are SpmvTransport's.
+enum DotRegime { DOT_TICKET = 0, DOT_WAVE = 1, DOT_HAND = 2 };      // tickets / tail finish, consumer-side finish, hand-over
+// what happens to the group: NOW / DEFER open one (closed at once / riding across the next product); FORCE: the host or a product
+// needs the open group's scalars before a consumer came; CONSUME: the consuming kernel's launch; CONTRIBUTE: a producer that
+// neither opens nor closes (a product without dots; the first of two producers of one group)
+enum DotEvent { DOT_NOW = 0, DOT_DEFER = 1, DOT_FORCE = 2, DOT_CONSUME = 3, DOT_CONTRIBUTE = 4 };
+enum DotOpen { DOT_OPEN_NONE = 0, DOT_OPEN_PLAIN = 1, DOT_OPEN_DEFERRED = 2, DOT_OPEN_STAGED = 3 };   // the group open when the call is made
+struct DotShape {
+    int transport = SPMV_SINGLE;
+    bool stream_ordered = false, overlap = false;      // hosted: the transport's collectives run in stream order; two streams
+    bool inline_apply = false;                         // peer-to-peer: the producer's last workgroup may collect and apply
+    bool tail_finish = false;                          // the switch is on and the tables exist
+    bool graph_replay = false;                         // iterations are captured and replayed (BICG_GRAPH=1)
+    bool handover = false;                             // the switch is on, the tables exist and the product's layout allows it
+};
+struct DotCall {
+    int regime = DOT_TICKET, n = 0, off = 0, phase = 0;
+    bool apply_single = true;
+    int event = DOT_NOW, open = DOT_OPEN_NONE;
+    bool by_product = false;                           // the call comes from a product (its own dots, or it meets the open group)
+};
+enum DotOp {
+    DOT_OP_NOTHING = 0,        // the producer's last workgroup did it
+    DOT_OP_FINISH = 1,         // stand-alone finish (roles)
+    DOT_OP_ALLREDUCE = 2, DOT_OP_APPLY = 3, DOT_OP_APPLY_P2P = 4,
+    DOT_OP_RECORD = 5, DOT_OP_WAIT = 6,      // an event recorded on `stream` / `stream` waits for the event recorded last
+    DOT_OP_STAGE = 7,          // staged by the next product's first launch (roles)
+    DOT_OP_CONSUMER = 8,       // finished by the consuming kernel (roles)
+};
+enum DotWhen { DOT_AT_CLOSE = 0, DOT_BEHIND_HALO = 1, DOT_AFTER_PRODUCT = 2, DOT_IN_CONSUMER = 3 };
+enum DotStream { DOT_COMPUTE = 0, DOT_COMM = 1 };
+enum DotPlanError { DOT_PLAN_OK = 0, DOT_ERR_OPEN = 1, DOT_ERR_STAGE_DOTS = 2, DOT_ERR_HAND_NONE = 3 };
+struct DotStep { int op = DOT_OP_NOTHING, when = DOT_AT_CLOSE, stream = DOT_COMPUTE, roles = 0, n = 0, off = 0, phase = 0; };
+constexpr int kDotMaxSteps = 7;
+struct DotPlan {
+    int error = DOT_PLAN_OK;
+    bool wave = false, hand = false, apply_now = false;      // the producer's Reduce ...
+    int n_collect = 0;                                        // ... its p2p.n_collect
+    bool tail = false;                                        // ... carries a new tail tag
+    bool mailbox = false;                                     // ... publishes to the peers' mailboxes (carries the group's descriptor)
+    bool deferred = false;                                    // the group rides across the next product
+    int nsteps = 0;
+    DotStep step[kDotMaxSteps];
+};
+bool dot_tail_available(const DotShape &s);      // can a ticket group take the tail finish
+bool dot_handover(const DotShape &s);            // does plain BiCGStab hand its groups over to the consuming kernels
+DotPlan dot_group_plan(const DotShape &s, const DotCall &k);
+const char *dot_plan_error(int error);           // the message the executor ends the program with
+// bicg_dot_group_plan (include/bicgstab_hip.h section 5): lengths of its arrays
+constexpr int kDotShapeLen = 7, kDotCallLen = 8, kDotPlanLen = 9, kDotStepLen = 7;
 
 // BICG_PLAN="reorder=1|2" (bicg_reorder.cpp; C views: bicg_reorder_plan / bicg_permute_block, include/bicgstab_hip.h section 5).
 // reorder_rcm: perm[new] = old, reverse Cuthill-McKee on the symmetrised pattern, and the eight stats of bicg_reorder_plan.

@@ -113,14 +113,9 @@ static ShiftDev shifted_setup(bicg_ctx *c, int mode, const double *x_set_host, c
         c->trace_cap = o.max_iter > 0 ? o.max_iter : 1;
         c->trace = c->own.regrow(c->trace, 4 * (size_t)c->trace_cap);
     }
-    Scal hs;
-    memset(&hs, 0, sizeof hs);
-    hs.tol2 = o.tol * o.tol; hs.max_iter = o.max_iter;
-    hs.tr_alpha = c->trace; hs.tr_omega = c->trace + c->trace_cap;
-    hs.tr_beta = c->trace + 2 * (size_t)c->trace_cap; hs.tr_dotr = c->trace + 3 * (size_t)c->trace_cap;
+    Scal hs = scal_block(c, o);
     hs.sh = c->sh_dev;
-    BICG_HIP(hipMemcpyAsync(c->S, &hs, sizeof hs, hipMemcpyHostToDevice, c->sc));
-    BICG_HIP(hipMemsetAsync(c->counter, 0, sizeof(unsigned) * (kShards + 1) * kCounterStride, c->sc));
+    c->dots.reset(false, &hs);           // the shifted solvers keep the ticket reductions (scalars applied in place)
     BICG_HIP(hipMemsetAsync(c->slab + 2 * st, 0, sizeof(double) * 10 * st, c->sc));
     c->time_kernels = false;
     sec_begin(c, (o.time_kernels & 2) != 0); c->sec_dump = (o.time_kernels & 4) != 0;
@@ -138,7 +133,6 @@ int run_switching(bicg_ctx *c, int mode, double *x_set_host, double *r_host, con
     if (o.max_iter < 0) o.max_iter = 0;
     if (o.check_every < 1) o.check_every = 1;
     use_device(c);
-    c->wave_mode = false;                // the shifted solvers keep the ticket reductions (scalars applied in place)
     c->spmv_dir = 0;                     // same first direction for every solve on this context (see run_begin)
     const size_t st = c->stride, n = c->n_loc;
 
@@ -159,8 +153,8 @@ int run_switching(bicg_ctx *c, int mode, double *x_set_host, double *r_host, con
     double *qc = v.z;                               // q_copy (:394)
     const double t0 = now_sec();
     c->cur_has_shift = false;
-    launch_shift_init(v, c->p_set + (size_t)seed * st, c->S, c->red(0, PH_SW_INIT, true, 1), c->sc);   // r# = r, (r,r)
-    group_now(c, 1, PH_SW_INIT);
+    launch_shift_init(v, c->p_set + (size_t)seed * st, c->S, c->dots.open(1, PH_SW_INIT), c->sc);   // r# = r, (r,r)
+    c->dots.close();
     c->cur_has_shift = true;
     int switches = 0;
     for (;;) {
@@ -192,15 +186,15 @@ int run_switching(bicg_ctx *c, int mode, double *x_set_host, double *r_host, con
         sec_mark(c, SEC_VEC);
         for (int j = 0; j < chunk; ++j) {
             c->cur_k = c->hS->k + j + 1; c->cur_prod = 1; sec_remark(c);
-            spmv(c, p_seed, v.s, 1, v.rh, c->red(0, PH_SW_ALPHA, true, 1));           // s = (A + sigma I) p[seed], (r#,s)
-            group_now(c, 1, PH_SW_ALPHA);
+            spmv(c, p_seed, v.s, 1, v.rh, c->dots.open(1, PH_SW_ALPHA));           // s = (A + sigma I) p[seed], (r#,s)
+            c->dots.close();
             launch_sw_q(v, qc, c->S, c->sc);                                          // r_old, q
             c->cur_prod = 2;
-            spmv(c, v.r, v.y, 3, v.r, c->red(0, PH_SW_OMEGA, true, 2));               // y = (A + sigma I) q, (q,y), (q,q)
+            spmv(c, v.r, v.y, 3, v.r, c->dots.open(2, PH_SW_OMEGA));               // y = (A + sigma I) q, (q,y), (q,q)
             c->cur_prod = 0;
-            group_now(c, 2, PH_SW_OMEGA);
-            launch_sw_seed(v, x_seed, p_seed, c->S, c->red(0, PH_SW_END, true, 2), c->sc);   // x[seed], r, (r,r), (r#,r)
-            group_now(c, 2, PH_SW_END);
+            c->dots.close();
+            launch_sw_seed(v, x_seed, p_seed, c->S, c->dots.open(2, PH_SW_END), c->sc);   // x[seed], r, (r,r), (r#,r)
+            c->dots.close();
             {
                 Section sec(c, SEC_SHIFT);       // the shift loops of src/shifted_switching_solver.c:425-480
                 launch_sw_shifts(v, qc, c->p_set, c->x_set, (uint32_t)st, seed, c->sh_dev, c->S, c->sc);
@@ -249,7 +243,7 @@ bool persist_chunk_shifted(bicg_ctx *c, int mode, int niter, int it0, int nsig, 
 {
     const bool pipe = mode == SH_PIPE;          // else shifted_lopbicgstab: three groups and two products per iteration, numbered
                                                 // like the plain kernel's (fixed counts, advanced here)
-    if (c->grp.active) die("internal", "persistent chunk with an open dot group");
+    if (c->dots.is_open()) die("internal", "persistent chunk with an open dot group");
     const size_t st = c->stride;
     PersistArgs a = c->persist;
     a.v = c->v;
@@ -264,19 +258,7 @@ bool persist_chunk_shifted(bicg_ctx *c, int mode, int niter, int it0, int nsig, 
         a.set_nt = ws > 0.5 * 256.0 * 1048576.0;
         if (const char *e = knob_x("BICG_SHP_NT")) a.set_nt = atoi(e) != 0;
     }
-    a.timeout_ticks = c->p2p ? c->p2p->timeout_ticks : 200000000ull;
-    static const int xcd_map = knob_x("BICG_PERSIST_XCD") ? atoi(knob_x("BICG_PERSIST_XCD")) : 1;
-    a.xcd_map = xcd_map;
-    static const int first_sleep = knob_x("BICG_PERSIST_SLEEP") ? atoi(knob_x("BICG_PERSIST_SLEEP")) : 1;
-    a.first_sleep = (unsigned)first_sleep;
-    if (!pipe) c->persist_seq += 3u * (unsigned)niter;
-    if (a.multi) {
-        a.halo_seq0 = c->halo_seq;
-        a.p2p = c->p2p->red_desc(c->p2p->red_seq);
-        if (!pipe) { c->halo_seq += 2u * (unsigned)niter; c->p2p->red_seq += 3u * (unsigned)niter; }
-        a.ring = c->halo_ring;
-        c->halo_unsynced = 0;
-    }
+    persist_args(c, a, 3u, pipe ? 0u : (unsigned)niter);
     const hipError_t err = pipe ? launch_shpipe_persist(a, c->sc) : launch_shlop_persist(a, c->sc);
     if (err != hipSuccess) {
         if (c->nranks > 1) die("persistent kernel", "launch failed on a multi-rank run (BICG_PERSIST=0 selects the multi-launch iteration)");
@@ -300,7 +282,6 @@ int run_shifted(bicg_ctx *c, int mode, double *x_set_host, double *r_host, const
     if (o.max_iter < 0) o.max_iter = 0;
     if (o.check_every < 1) o.check_every = 1;
     use_device(c);
-    c->wave_mode = false;                // the shifted solvers keep the ticket reductions (scalars applied in place)
     c->spmv_dir = 0;                     // same first direction for every solve on this context (see run_begin)
     const size_t st = c->stride, n = c->n_loc;
 
@@ -321,14 +302,14 @@ int run_shifted(bicg_ctx *c, int mode, double *x_set_host, double *r_host, const
     const bool shifted_A = mode != SH_XI;       // lop / pipe iterate on A + sigma[seed] I, shifted_bicgstab on A
     const double t0 = now_sec();
     c->cur_has_shift = false;
-    launch_shift_init(v, p_seed, c->S, c->red(0, PH_SH_INIT, true, 1), c->sc);
-    group_now(c, 1, PH_SH_INIT);
+    launch_shift_init(v, p_seed, c->S, c->dots.open(1, PH_SH_INIT), c->sc);
+    c->dots.close();
     c->cur_shift = sigma[seed]; c->cur_has_shift = shifted_A;
     if (mode == SH_PIPE) {                                                   // src/shifted_solver.c:764-769, 785-786
-        spmv(c, v.r, v.w, 1, v.r, c->red(0, PH_SHP_INIT_ALPHA));             // w = (A + sigma I) r, (r,w)
-        group_defer(c, 1, PH_SHP_INIT_ALPHA);
-        spmv(c, v.w, v.t, 0, nullptr, c->red(0, PH_NONE));                   // t = (A + sigma I) w
-        group_flush(c);
+        spmv(c, v.r, v.w, 1, v.r, c->dots.open(1, PH_SHP_INIT_ALPHA, DOT_DEFER));             // w = (A + sigma I) r, (r,w)
+        c->dots.close();
+        spmv(c, v.w, v.t, 0, nullptr, c->dots.no_dots());                   // t = (A + sigma I) w
+        c->dots.flush();
     }
     fetch_scal(c);
     int it = 0;
@@ -355,29 +336,29 @@ int run_shifted(bicg_ctx *c, int mode, double *x_set_host, double *r_host, const
         }
         for (int j = 0; j < chunk && !persist; ++j) {
             if (mode == SH_PIPE) {
-                launch_shift_pipe1(v, p_seed, c->S, c->red(0, PH_SHP_OMEGA), c->sc);    // p, s, z, r_old, q, y, 2 dots
-                group_defer(c, 2, PH_SHP_OMEGA);
-                spmv(c, v.z, v.v, 0, nullptr, c->red(0, PH_NONE));                      // v = (A + sigma I) z
+                launch_shift_pipe1(v, p_seed, c->S, c->dots.open(2, PH_SHP_OMEGA, DOT_DEFER), c->sc);    // p, s, z, r_old, q, y, 2 dots
+                c->dots.close();
+                spmv(c, v.z, v.v, 0, nullptr, c->dots.no_dots());                      // v = (A + sigma I) z
                 {   // the shift loops of src/shifted_solver.c:850-905, with the seed system's x / r / w and the five dots in the same pass
                     Section sec(c, SEC_SHIFT);
-                    launch_shift_pipe2(v, c->p_set, c->x_set, (uint32_t)st, seed, c->sh_dev, c->S, c->red(0, PH_SHP_END), c->sc);
+                    launch_shift_pipe2(v, c->p_set, c->x_set, (uint32_t)st, seed, c->sh_dev, c->S, c->dots.open(5, PH_SHP_END, DOT_DEFER), c->sc);
                 }
-                group_defer(c, 5, PH_SHP_END);
-                spmv(c, v.w, v.t, 0, nullptr, c->red(0, PH_NONE));                      // t = (A + sigma I) w
-                group_flush(c);
+                c->dots.close();
+                spmv(c, v.w, v.t, 0, nullptr, c->dots.no_dots());                      // t = (A + sigma I) w
+                c->dots.flush();
                 continue;
             }
-            spmv(c, p_seed, v.s, 1, v.rh, c->red(0, PH_SH_ALPHA, true, 1));          // s = (A [+ sigma I]) p[seed], (r#,s)
-            group_now(c, 1, PH_SH_ALPHA);
+            spmv(c, p_seed, v.s, 1, v.rh, c->dots.open(1, PH_SH_ALPHA));          // s = (A [+ sigma I]) p[seed], (r#,s)
+            c->dots.close();
             launch_shift_q(v, c->S, c->sc);                                 // r_old = r, q = r - alpha s
             // lop: (q,y), (q,q) ; shifted_bicgstab: (q,y), (y,y)
-            spmv(c, v.r, v.y, mode == SH_XI ? 2 : 3, v.r, c->red(0, PH_SH_OMEGA, true, 2));
-            group_now(c, 2, PH_SH_OMEGA);
+            spmv(c, v.r, v.y, mode == SH_XI ? 2 : 3, v.r, c->dots.open(2, PH_SH_OMEGA));
+            c->dots.close();
             {   // the shift loops of src/shifted_solver.c:132-154 and 180-208, with the seed system's x / r and two dots in the same pass
                 Section sec(c, SEC_SHIFT);
-                launch_shift_update(v, c->p_set, c->x_set, (uint32_t)st, seed, c->sh_dev, c->S, c->red(0, PH_SH_END, true, 2), c->sc);
+                launch_shift_update(v, c->p_set, c->x_set, (uint32_t)st, seed, c->sh_dev, c->S, c->dots.open(2, PH_SH_END), c->sc);
             }
-            group_now(c, 2, PH_SH_END);
+            c->dots.close();
             launch_shift_pseed(v, p_seed, c->S, c->sc);                     // p[seed] = r + beta (p[seed] - omega s)
         }
         it += chunk;

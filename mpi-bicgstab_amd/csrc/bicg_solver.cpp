@@ -12,10 +12,6 @@
 #include "bicg_host.h"
 
 
-// ---------------------------------------------------------------- dot groups: consumer-side finish
-// (the four solvers of reference src/solver.c; struct Finish in bicg_device.h). A group is PRODUCED by
-// one or two kernels (per-wavefront partials), then CONSUMED by the kernel that needs the scalars,
-// by an SpMV that only has to deposit the sums, or by the stand-alone finisher.
 // ---------------------------------------------------------------- section timing
 void sec_mark(bicg_ctx *c, int label)
 {
@@ -67,154 +63,8 @@ void sec_collect(bicg_ctx *c, int iters)
     c->sec_iters = iters;
 }
 
-Reduce grp_produce(bicg_ctx *c, int off, int n, int phase, unsigned nwg)
-{
-    if (c->grp.active) die("internal", "a dot group was produced while the previous one was still open");
-    bicg_ctx::Group &g = c->grp;
-    g = bicg_ctx::Group{};
-    g.active = true;
-    g.seq = ++c->grp_seq;
-    g.n = n; g.off = off; g.phase = phase; g.buf = (int)(g.seq & 1u);
-    g.nparts = nwg * (kBlock / 64);               // SpMV producers: set by spmv()
-    if (c->p2p) g.mail_seq = c->p2p->red_seq++;
-    Reduce r{};
-    r.partial = c->wpart[g.buf];
-    r.wave = 1; r.red_off = off; r.phase = phase;
-    return r;
-}
-
-Finish grp_desc(bicg_ctx *c, int roles)
-{
-    const bicg_ctx::Group &g = c->grp;
-    Finish f{};
-    f.partial = c->wpart[g.buf]; f.nparts = g.nparts; f.seq = g.seq;
-    f.shard = c->shard_ll + (size_t)g.buf * kShardLL * kRedSlots * 2;
-    f.shard_clear = c->shard_ll + (size_t)(g.buf ^ 1) * kShardLL * kRedSlots * 2;
-    f.n = g.n; f.red_off = g.off; f.phase = g.phase; f.roles = roles;
-    f.spin_ticks = c->spin_ticks;
-    if (c->p2p) { f.p2p = c->p2p->red_desc(g.mail_seq); f.alarm = c->alarm; }
-    return f;
-}
-
-// stand-alone finisher, in place on the current scalar block. local_only: deposit this rank's sums
-// and leave the recurrence to the all-reduce + apply kernel the host enqueues next.
-void grp_close(bicg_ctx *c, bool local_only)
-{
-    if (!c->grp.active) return;
-    Finish f = grp_desc(c, FIN_BLOCK0 | (c->grp.staged ? 0 : FIN_SHARDS | FIN_PUSH) | (local_only ? FIN_LOCAL : 0));
-    if (local_only) f.phase = PH_NONE;
-    launch_finish(Launch{c->S, f, c->sc});
-    c->grp.active = false;
-    if (c->p2p) c->halo_unsynced = 0;
-}
-
 // transports whose collectives the host enqueues (RCCL, host callbacks)
 bool hosted(const bicg_ctx *c) { return !c->single() && !c->p2p; }
-
-// Launch descriptor for an element-wise kernel of the four solvers; the open group (if any) is
-// finished by that kernel, and everything enqueued afterwards reads the scalar block it writes.
-Launch grp_consume(bicg_ctx *c)
-{
-    Launch L{c->S, Finish{}, c->sc};
-    if (!c->grp.active) return L;
-    L.fin = grp_desc(c, FIN_APPLY | (c->grp.staged ? 0 : FIN_SHARDS | FIN_PUSH));
-    c->cur ^= 1;
-    c->S = c->Sbuf + c->cur;
-    L.fin.Snext = c->S;
-    c->grp.active = false;
-    if (c->p2p) c->halo_unsynced = 0;      // an all-reduce is a barrier among the ranks
-    return L;
-}
-
-// The open group as seen by the next SpMV launch: a deferred group is staged (shards summed, sums on
-// their way to the peers) and stays open; anything else is closed first.
-Finish grp_for_spmv(bicg_ctx *c)
-{
-    bicg_ctx::Group &g = c->grp;
-    if (!g.active) return Finish{};
-    if (hosted(c)) { grp_close(c, true); return Finish{}; }
-    if (g.deferred) {
-        if (g.staged) return Finish{};
-        g.staged = true;
-        return grp_desc(c, FIN_SHARDS | FIN_PUSH);
-    }
-    grp_close(c);
-    return Finish{};
-}
-
-// ---------------------------------------------------------------- dot groups across ranks
-void group_enqueue(bicg_ctx *c, int n, int phase, hipEvent_t after)
-{
-    if (c->comm->stream_ordered()) {
-        BICG_HIP(hipStreamWaitEvent(c->sm, after, 0));
-        ctx_allreduce(c, c->S->red + c->pend_off, n, c->sm);
-        launch_apply(c->S, phase, c->sm);
-        hipEvent_t e = c->ev_red[c->i_red++ % kEvRing];
-        BICG_HIP(hipEventRecord(e, c->sm));
-        c->pend_ev = e;
-    } else {
-        ctx_allreduce(c, c->S->red + c->pend_off, n, c->sc);   // synchronises sc
-        launch_apply(c->S, phase, c->sc);
-        c->pend_ev = nullptr;
-    }
-}
-
-// all-reduce the n sums in Scal::red and apply `phase` before anything else runs on the compute
-// stream: nothing can overlap, so both are enqueued on the compute stream itself (a round trip
-// through the communication stream costs two cross-stream event hand-offs, ~10 us eager)
-void group_now(bicg_ctx *c, int n, int phase)
-{
-    if (c->wave_mode) {
-        // single rank / peer-to-peer: the group stays open for the kernel that consumes it
-        if (!hosted(c)) { c->grp.deferred = false; return; }
-        Section sec(c, SEC_REDUCE);
-        const bicg_ctx::Group g = c->grp;
-        grp_close(c, true);                                   // this rank's sums -> Scal::red
-        ctx_allreduce(c, c->S->red + g.off, g.n, c->sc);
-        launch_apply(c->S, g.phase, c->sc);
-        return;
-    }
-    if (c->single()) return;   // applied in-kernel by the finishing workgroup
-    Section sec(c, SEC_REDUCE);
-    if (c->p2p) {              // the producers stored their sums into every rank's mailbox already
-        if (c->open_inline) {  // ... and the last of them collects and applies (Reduce::p2p.n_collect)
-            c->open_inline = false;
-            c->p2p->red_seq++;
-        } else {
-            launch_apply_p2p(c->S, phase, n, c->p2p->red_desc(c->p2p->red_seq++), c->p2p->timeout_ticks, c->sc);
-        }
-        c->halo_unsynced = 0;
-        return;
-    }
-    c->pend_off = 0;
-    ctx_allreduce(c, c->S->red, n, c->sc);
-    launch_apply(c->S, phase, c->sc);
-}
-
-// same, but the all-reduce is started by the NEXT spmv() after its halo exchange is in flight and
-// joined after that SpMV: the overlap of reference src/solver.c:363-367 and 377-385
-void group_defer(bicg_ctx *c, int n, int phase)
-{
-    if (c->wave_mode) {
-        if (!hosted(c)) { c->grp.deferred = true; return; }   // staged by the next SpMV launch, applied by the consumer
-        const bicg_ctx::Group g = c->grp;
-        if (!c->overlap || !c->comm->stream_ordered()) { group_now(c, n, phase); return; }
-        grp_close(c, true);
-        hipEvent_t e = c->ev_dots[c->i_dots++ % kEvRing];
-        BICG_HIP(hipEventRecord(e, c->sc));
-        c->pend = true; c->pend_n = g.n; c->pend_off = g.off; c->pend_phase = g.phase; c->pend_ev = e;
-        return;
-    }
-    if (c->single()) return;
-    if (c->p2p) {   // collected after the next SpMV: the sums cross the links while it runs
-        c->pend = true; c->pend_n = n; c->pend_phase = phase; c->pend_seq = c->p2p->red_seq++;
-        return;
-    }
-    if (!c->overlap || !c->comm->stream_ordered()) { group_now(c, n, phase); return; }
-    hipEvent_t e = c->ev_dots[c->i_dots++ % kEvRing];
-    BICG_HIP(hipEventRecord(e, c->sc));
-    c->pend = true; c->pend_n = n; c->pend_off = 0; c->pend_phase = phase; c->pend_ev = e;
-}
 
 // every row on the sliced-ELL path, and the plan found a grid's 7-point stencil (build_stencil_plan)
 bool stencil_product(const bicg_ctx *c)
@@ -311,7 +161,7 @@ static bool launch_step(bicg_ctx *c, SpmvArgs &a, const SpmvStep &t, int ndot, i
 // workgroup as (0 + sum_diag) + sum_offd, the reference's order.
 // Which launches that takes, over which lists and with which partial slots: spmv_plan (bicg_spmv_plan.cpp). Here the plan is
 // enqueued: start the exchange, the steps that do not read the halo, land it, the steps that do, the joins.
-// fin: a dot group of earlier kernels that the first kernel launched here finishes (grp_for_spmv).
+// fin: a dot group of earlier kernels that the first kernel launched here finishes (DotGroups::before_product).
 void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Reduce red, Finish fin, int epi,
           Scal *S)
 {
@@ -346,8 +196,7 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
     red.expected = plan.expected; red.slot_base = 0;
     if (!plan.tail) red.tail_seq = 0;
     a.red = red;
-    if (red.hand) c->hand.nsh = plan.hand_nsh;
-    if (plan.sets_nparts) c->grp.nparts = plan.expected * (kBlock / 64);
+    c->dots.producer_grid(red, plan.expected, plan.hand_nsh, plan.sets_nparts);
 
     // per-kernel timing: every SpMV kernel of this call gets its own start/stop event pair
     const bool timed = c->time_kernels && c->tev_used + 8 <= (int)c->tev.size();
@@ -363,7 +212,7 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
 
     const bool multi = !c->single(), host = hosted(c);
     unsigned seq = 0;
-    bool send = true, joined_pending = false;
+    bool send = true;
     hipEvent_t landed = nullptr;
     if (c->p2p) {
         seq = p2p_next_exchange(c, Sh);
@@ -381,12 +230,7 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
         if (host) { c->cur_sub = 1; sec_remark(c); }      // the exchange: the reference's "agv" section (src/matrix.c:432)
         landed = halo_start(c, xin, Sh, seq, send, shape.own_stream);
         if (host) { c->cur_sub = 0; sec_remark(c); }
-        if (host && c->pend) {   // start the deferred all-reduce behind the halo traffic
-            hipEvent_t after = c->pend_ev;
-            c->pend = false;
-            group_enqueue(c, c->pend_n, c->pend_phase, after);
-            joined_pending = true;
-        }
+        if (host) c->dots.behind_halo();      // a deferred all-reduce starts behind the halo traffic
     }
     run(false);
     if (multi && !plan.fused) halo_land(c, xin, Sh, seq, landed);
@@ -394,15 +238,7 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
     if (second) { c->cur_sub = 2; sec_remark(c); }
     run(true);
     if (second) { c->cur_sub = 0; sec_remark(c); }
-    if (c->p2p && c->pend) {
-        c->pend = false;
-        launch_apply_p2p(c->S, c->pend_phase, c->pend_n, c->p2p->red_desc(c->pend_seq), c->p2p->timeout_ticks, c->sc);
-        c->halo_unsynced = 0;
-    }
-    if (joined_pending && c->pend_ev) {
-        BICG_HIP(hipStreamWaitEvent(c->sc, c->pend_ev, 0));
-        c->pend_ev = nullptr;
-    }
+    c->dots.after_product();                      // ... and is joined here; peer-to-peer: collected and applied here
     if (a.fin.seq) {   // no SpMV kernel was launched (a rank without work): finish the group on its own
         Finish f = a.fin;
         f.roles |= FIN_BLOCK0;
@@ -414,18 +250,13 @@ void spmv(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, Red
 
 // SpMV of the pipelined solvers (consumer-side finish): a deferred group of earlier kernels is staged
 // by this launch; the SpMV's own dots (ndot > 0) open the next group.
-void spmv_grp(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, int phase)
+void spmv_grp(bicg_ctx *c, double *xin, double *yout, int ndot, const double *u, int phase, int event)
 {
-    const Finish fin = grp_for_spmv(c);
+    const Finish fin = c->dots.before_product(ndot > 0);
     Reduce red{};
-    if (ndot > 0) {
-        if (c->grp.active) {     // a deferred group is still open: an SpMV with dots of its own cannot carry it
-            if (fin.seq) die("internal", "an SpMV with dots was asked to stage a deferred group");
-            grp_close(c);
-        }
-        red = grp_produce(c, 0, ndot, phase, 0);
-    }
+    if (ndot > 0) red = c->dots.open(ndot, phase, event, 0, 0, true);
     spmv(c, xin, yout, ndot, u, red, fin);
+    if (ndot > 0) c->dots.close();
 }
 
 // The halo exchange of spmv() on its own: afterwards xin[rows .. rows + halo) holds the other ranks' values.
@@ -554,34 +385,13 @@ void spmm_buffers(bicg_ctx *c)
 
 // SpMV whose epilogue runs a pipelined phase on the workgroup's own rows (k_spmv_sell_epi): the open dot group is
 // summed by the launch's first workgroups and applied at the epilogue; the phase's own nd dots open the next group.
-void spmv_epi(bicg_ctx *c, double *xin, double *yout, int epi, int nd, int phase)
+void spmv_epi(bicg_ctx *c, double *xin, double *yout, int epi, int nd, int phase, int event)
 {
-    const Launch L = grp_consume(c);
-    Reduce red = grp_produce(c, 0, nd, phase, 0);
+    const Launch L = c->dots.consume();
+    Reduce red = c->dots.open(nd, phase, event);
     spmv(c, xin, yout, 0, nullptr, red, L.fin, epi, L.S);
+    c->dots.close();
 }
-
-// a deferred group that no SpMV picked up (defensive)
-void group_flush(bicg_ctx *c)
-{
-    if (c->wave_mode && !hosted(c)) return;      // consumed by the next element-wise kernel or by fetch_scal
-    if (!c->pend) return;
-    Section sec(c, SEC_REDUCE);
-    if (c->p2p) {
-        c->pend = false;
-        launch_apply_p2p(c->S, c->pend_phase, c->pend_n, c->p2p->red_desc(c->pend_seq), c->p2p->timeout_ticks, c->sc);
-        c->halo_unsynced = 0;
-        return;
-    }
-    hipEvent_t after = c->pend_ev;
-    c->pend = false;
-    group_enqueue(c, c->pend_n, c->pend_phase, after);
-    if (c->pend_ev) BICG_HIP(hipStreamWaitEvent(c->sc, c->pend_ev, 0));
-    c->pend_ev = nullptr;
-}
-
-void fetch_scal(bicg_ctx *c);
-
 
 // Hand-over of plain BiCGStab's dot groups (struct Reduce / FIN_HAND): one rank, tail finish, eager launches, and every product of
 // the iteration a single launch of k_spmv_sell on padded slices with 16-bit offsets and streamed values -- the layout whose
@@ -589,9 +399,24 @@ void fetch_scal(bicg_ctx *c);
 // 32-bit layout keeps 12 bytes of it with two dots, the list-driven ones run at five or six wavefronts whatever their epilogue).
 bool plain_handover(const bicg_ctx *c)
 {
-    return c->handover && c->single() && !c->p2p && c->tail_finish && c->tail_tab && c->hand_shard && c->graph_mode != 1 &&
-           c->nblk == 0 && c->glist_all && c->sell_entries > 0 && !c->sell.jag && !c->sell.win_slots && c->sell.col16 && !c->sell.vbase &&
-           c->ng_bnd == 0 && c->n_int == 0 && c->n_bnd == 0 && !stencil_product(c);
+    DotShape s = c->dots.shape();      // switch and tables; here: the layout
+    s.handover = s.handover && c->nblk == 0 && c->glist_all && c->sell_entries > 0 && !c->sell.jag && !c->sell.win_slots && c->sell.col16 &&
+                 !c->sell.vbase && c->ng_bnd == 0 && c->n_int == 0 && c->n_bnd == 0 && !stencil_product(c);
+    return dot_handover(s);
+}
+
+// the scalar block a solve starts from: tolerance, iteration limit, where the trace goes
+Scal scal_block(const bicg_ctx *c, const bicg_options &o)
+{
+    Scal h;
+    memset(&h, 0, sizeof h);
+    h.tol2 = o.tol * o.tol;
+    h.max_iter = o.max_iter;
+    h.tr_alpha = c->trace;
+    h.tr_omega = c->trace + c->trace_cap;
+    h.tr_beta = c->trace + 2 * (size_t)c->trace_cap;
+    h.tr_dotr = c->trace + 3 * (size_t)c->trace_cap;
+    return h;
 }
 
 // ---------------------------------------------------------------- the four iterations
@@ -608,14 +433,15 @@ struct Driver {
     // element-wise kernel without / with dots: it finishes the open group, then opens its own
     template <class Fn> void vec(Fn launch)
     {
-        const Launch L = grp_consume(c);
+        const Launch L = c->dots.consume();
         launch(v, L);
     }
-    template <class Fn> void vec_dots(Fn launch, int n, int phase)
+    template <class Fn> void vec_dots(Fn launch, int n, int phase, int event)
     {
-        const Launch L = grp_consume(c);
-        const Reduce r = grp_produce(c, 0, n, phase, vg);
+        const Launch L = c->dots.consume();
+        const Reduce r = c->dots.open(n, phase, event, 0, vg);
         launch(v, L, r);
+        c->dots.close();
     }
 
     // plain and CA-BiCGStab: ticket reductions, scalars applied in place by the producer's last workgroup
@@ -625,54 +451,26 @@ struct Driver {
     {
         const bool plain = method == BICG_BICGSTAB || hat != Precond::NONE;      // the plain iteration, preconditioned or not
         const bool rr = method == BICG_PIPE_BICGSTAB_RR || (method == BICG_PIPE_BICGSTAB && c->opt.rr_drift > 0.0);
-        if (!c->wave_mode) {
-            spmv(c, v.x, v.ax, 0, nullptr, c->red(0, PH_NONE));                       // Ax = A x0
+        if (!c->dots.wave_mode) {
+            spmv(c, v.x, v.ax, 0, nullptr, c->dots.no_dots());                       // Ax = A x0
             // r = b - Ax, r# = r, (r,r); the plain iterations: p = r; DIAGONAL: and p^ = dinv o p in the same pass
-            if (hat == Precond::DIAGONAL) launch_init_residual_diag(v, c->pc.planes, here(), c->red(0, PH_INIT, true, 1));
-            else launch_init_residual(v, plain, rr, here(), c->red(0, PH_INIT, true, 1));
-            group_now(c, 1, PH_INIT);
+            if (hat == Precond::DIAGONAL) launch_init_residual_diag(v, c->pc.planes, here(), c->dots.open(1, PH_INIT));
+            else launch_init_residual(v, plain, rr, here(), c->dots.open(1, PH_INIT));
+            c->dots.close();
             if (hat == Precond::BLOCK) precond_apply(c, v.p, v.z);                    // p^ = M^-1 p
             if (plain) return;
-            spmv(c, v.r, v.w, 1, v.r, c->red(0, PH_INIT_ALPHA, true, 1));             // w = A r, (r,w)
-            group_now(c, 1, PH_INIT_ALPHA);
+            spmv(c, v.r, v.w, 1, v.r, c->dots.open(1, PH_INIT_ALPHA));             // w = A r, (r,w)
+            c->dots.close();
             return;
         }
         spmv_grp(c, v.x, v.ax);                                                    // Ax = A x0
-        vec_dots([&](const Vecs &vv, const Launch &L, Reduce r) { launch_init_residual(vv, plain, rr, L, r); }, 1, PH_INIT);
-        group_now(c, 1, PH_INIT);
-        spmv_grp(c, v.r, v.w, 1, v.r, PH_INIT_ALPHA);                              // w = A r, (r,w)
-        group_defer(c, 1, PH_INIT_ALPHA);                                           // overlaps t = A w (src/solver.c:339-343)
+        vec_dots([&](const Vecs &vv, const Launch &L, Reduce r) { launch_init_residual(vv, plain, rr, L, r); }, 1, PH_INIT, DOT_NOW);
+        spmv_grp(c, v.r, v.w, 1, v.r, PH_INIT_ALPHA, DOT_DEFER);                   // w = A r, (r,w); overlaps t = A w (src/solver.c:339-343)
         spmv_grp(c, v.w, v.t);
-        group_flush(c);
+        c->dots.flush();
     }
 
     bool handover() const { return plain_handover(c); }
-    // the producer's side: its last workgroups leave the shard totals in the table the previous group does not use
-    Reduce hand_produce(int phase, int n)
-    {
-        Reduce r = c->red(0, phase, true, n);
-        bicg_ctx::Hand &h = c->hand;
-        h.buf ^= 1; h.seq = r.tail_seq; h.n = n; h.phase = phase;
-        r.hand = 1; r.apply_now = 0;
-        r.tail_shard = c->hand_shard + (size_t)h.buf * kRedSlots * kShards * 2;
-        return r;
-    }
-    // the consumer's side: it reads the current scalar block and the open group's totals and writes the other block, which is
-    // what everything enqueued from now on (and the host) reads
-    Launch hand_consume()
-    {
-        const bicg_ctx::Hand &h = c->hand;
-        if (!h.seq) die("internal", "hand-over: a consumer without an open dot group");
-        Launch L{c->S, Finish{}, c->sc};
-        L.fin.seq = h.seq; L.fin.nparts = h.nsh; L.fin.n = h.n; L.fin.red_off = 0; L.fin.phase = h.phase; L.fin.roles = FIN_HAND;
-        L.fin.shard = c->hand_shard + (size_t)h.buf * kRedSlots * kShards * 2;
-        c->cur ^= 1;
-        c->S = c->Sbuf + c->cur;
-        L.fin.Snext = c->S;
-        c->hand.seq = 0;
-        return L;
-    }
-
     // Plain BiCGStab, as it stands or right-preconditioned (`hat`; DESIGN.md sections 4.20, 4.21): one sequence of operations, dot
     // groups and phases. Preconditioned, the products take the hat vectors p^ = M^-1 p (v.z) and q^ = M^-1 q (v.w) -- idle in the
     // plain iteration, zeroed with their halo tails by run_begin -- and x is updated with them; r stays the residual of the caller's
@@ -683,28 +481,27 @@ struct Driver {
     void iter_plain()   // reference src/solver.c:88-119
     {
         if (hat == Precond::NONE && handover()) {
-            spmv(c, v.p, v.s, 1, v.rh, hand_produce(PH_PLAIN_ALPHA, 1));      // s = A p, (r#,s)
-            launch_plain_q(v, hand_consume());                                // -> alpha ; q = r - alpha s
-            spmv(c, v.r, v.y, 2, v.r, hand_produce(PH_OMEGA, 2));             // y = A q, (q,y), (y,y)
-            const Launch L = hand_consume();                                  // -> omega ; x, r, (r,r), (r#,r)
-            const Reduce r = hand_produce(PH_PLAIN_END, 2);
-            c->hand.nsh = std::min<unsigned>(vg, (unsigned)kShards);
-            launch_plain_xr(v, L, r);
-            launch_plain_p(v, hand_consume());                                // -> beta, k++ ; p = r + beta (p - omega s)
+            DotGroups &d = c->dots;
+            spmv(c, v.p, v.s, 1, v.rh, d.open_hand(1, PH_PLAIN_ALPHA));       // s = A p, (r#,s)
+            launch_plain_q(v, d.consume_hand());                              // -> alpha ; q = r - alpha s
+            spmv(c, v.r, v.y, 2, v.r, d.open_hand(2, PH_OMEGA));              // y = A q, (q,y), (y,y)
+            const Launch L = d.consume_hand();                                // -> omega ; x, r, (r,r), (r#,r)
+            launch_plain_xr(v, L, d.open_hand(2, PH_PLAIN_END, vg));
+            launch_plain_p(v, d.consume_hand());                              // -> beta, k++ ; p = r + beta (p - omega s)
             return;
         }
         const double *dinv = c->pc.planes;
-        spmv(c, hat ? v.z : v.p, v.s, 1, v.rh, c->red(0, PH_PLAIN_ALPHA, true, 1));   // s = A p (A p^), (r#,s) -> alpha
-        group_now(c, 1, PH_PLAIN_ALPHA);
+        spmv(c, hat ? v.z : v.p, v.s, 1, v.rh, c->dots.open(1, PH_PLAIN_ALPHA));   // s = A p (A p^), (r#,s) -> alpha
+        c->dots.close();
         if (hat == Precond::DIAGONAL) launch_diag_q(v, dinv, here());   // q = r - alpha s (in v.r) ; q^ = dinv o q
         else launch_plain_q(v, here());
         if (hat == Precond::BLOCK) precond_apply(c, v.r, v.w);          // q^ = M^-1 q
-        spmv(c, hat ? v.w : v.r, v.y, 2, v.r, c->red(0, PH_OMEGA, true, 2));          // y = A q (A q^), (q,y), (y,y) -> omega
-        group_now(c, 2, PH_OMEGA);
+        spmv(c, hat ? v.w : v.r, v.y, 2, v.r, c->dots.open(2, PH_OMEGA));          // y = A q (A q^), (q,y), (y,y) -> omega
+        c->dots.close();
         // x += alpha p + omega q (alpha p^ + omega q^), r, (r,r), (r#,r) -> beta, k++
-        if (hat) launch_diag_xr(v, here(), c->red(0, PH_PLAIN_END, true, 2));
-        else launch_plain_xr(v, here(), c->red(0, PH_PLAIN_END, true, 2));
-        group_now(c, 2, PH_PLAIN_END);
+        if (hat) launch_diag_xr(v, here(), c->dots.open(2, PH_PLAIN_END));
+        else launch_plain_xr(v, here(), c->dots.open(2, PH_PLAIN_END));
+        c->dots.close();
         if (hat == Precond::DIAGONAL) launch_diag_p(v, dinv, here());   // p = r + beta (p - omega s) ; p^ = dinv o p
         else launch_plain_p(v, here());
         if (hat == Precond::BLOCK) precond_apply(c, v.p, v.z);          // p^ = M^-1 p
@@ -715,15 +512,15 @@ struct Driver {
         launch_ca_ps(v, here());                                // p, s recurrences
         if (c->ca_fuse && c->single() && stencil_product(c) && !c->cur_has_shift) {
             // z = A s with q = r - alpha s, y = w - alpha z, (q,y), (y,y) on the product's own rows: s_i and z_i are registers there
-            spmv(c, v.s, v.z, 2, nullptr, c->red(0, PH_OMEGA, true, 2), Finish{}, 3);
+            spmv(c, v.s, v.z, 2, nullptr, c->dots.open(2, PH_OMEGA), Finish{}, 3);
         } else {
-            spmv(c, v.s, v.z, 0, nullptr, c->red(0, PH_NONE));   // z = A s
-            launch_qy(v, here(), c->red(0, PH_OMEGA, true, 2)); // q, y, (q,y), (y,y) -> omega
+            spmv(c, v.s, v.z, 0, nullptr, c->dots.no_dots());   // z = A s
+            launch_qy(v, here(), c->dots.open(2, PH_OMEGA)); // q, y, (q,y), (y,y) -> omega
         }
-        group_now(c, 2, PH_OMEGA);
-        launch_ca_xr(v, here(), c->red(0, PH_NONE, false));     // x, r, (r,r), (r#,r), (r#,s), (r#,z)
-        spmv(c, v.r, v.w, 1, v.rh, c->red(2, PH_RECUR_END, true, 5));     // w = A r, (r#,w) -> beta, alpha, k++
-        group_now(c, 5, PH_RECUR_END);
+        c->dots.close();
+        launch_ca_xr(v, here(), c->dots.contribute(0, false));     // x, r, (r,r), (r#,r), (r#,s), (r#,z)
+        spmv(c, v.r, v.w, 1, v.rh, c->dots.open(5, PH_RECUR_END, DOT_NOW, 2));     // w = A r, (r#,w) -> beta, alpha, k++
+        c->dots.close();
     }
 
     bool replaces(int it) const { return method == BICG_PIPE_BICGSTAB_RR && krr > 0 && (it % krr == 0) && it > 0 && it <= krr * nrr; }
@@ -731,7 +528,7 @@ struct Driver {
     // SpMV launch per product (one rank, or the peer-to-peer exchange folded into the launch)
     bool fused() const
     {
-        return c->fuse_pipe && c->wave_mode && !hosted(c) && c->fuse_plan_ok;
+        return c->fuse_pipe && c->dots.wave_mode && !hosted(c) && c->fuse_plan_ok;
     }
 
     // last: the caller looks at x / r after this iteration (end of a run_iterate call, adaptive replacement check):
@@ -741,24 +538,20 @@ struct Driver {
         const bool replace = force_replace || replaces(it);
         if (!replace) {
             if (!c->f1_done) {
-                vec_dots(launch_pipe_f1, 2, PH_OMEGA);                   // p, s, z, q, y, (q,y), (y,y)
-                group_defer(c, 2, PH_OMEGA);
+                vec_dots(launch_pipe_f1, 2, PH_OMEGA, DOT_DEFER);                   // p, s, z, q, y, (q,y), (y,y)
             }
             c->f1_done = false;
             if (fused()) {
-                spmv_epi(c, v.z, v.v, 1, 5, PH_RECUR_END);               // v = A z ; x, r, w, five dots   || all-reduce of (q,y), (y,y)
-                group_defer(c, 5, PH_RECUR_END);
+                spmv_epi(c, v.z, v.v, 1, 5, PH_RECUR_END, DOT_DEFER);               // v = A z ; x, r, w, five dots   || all-reduce of (q,y), (y,y)
                 if (!last && !replaces(it + 1)) {
-                    spmv_epi(c, v.w, v.t, 2, 2, PH_OMEGA);               // t = A w ; phase 1 of iteration it + 1   || all-reduce of the five
-                    group_defer(c, 2, PH_OMEGA);
+                    spmv_epi(c, v.w, v.t, 2, 2, PH_OMEGA, DOT_DEFER);               // t = A w ; phase 1 of iteration it + 1   || all-reduce of the five
                     c->f1_done = true;
                 } else {
                     spmv_grp(c, v.w, v.t);                               // t = A w   || all-reduce
                 }
             } else {
                 spmv_grp(c, v.z, v.v);                                   // v = A z   || all-reduce
-                vec_dots(launch_pipe_f2, 5, PH_RECUR_END);               // x, r, w, five dots
-                group_defer(c, 5, PH_RECUR_END);
+                vec_dots(launch_pipe_f2, 5, PH_RECUR_END, DOT_DEFER);               // x, r, w, five dots
                 spmv_grp(c, v.w, v.t);                                   // t = A w   || all-reduce
             }
         } else {
@@ -766,18 +559,16 @@ struct Driver {
             vec(launch_p_update);
             spmv_grp(c, v.p, v.s);                                   // s = A p
             spmv_grp(c, v.s, v.z);                                   // z = A s
-            vec_dots(launch_qy, 2, PH_OMEGA);
-            group_defer(c, 2, PH_OMEGA);
+            vec_dots(launch_qy, 2, PH_OMEGA, DOT_DEFER);
             spmv_grp(c, v.z, v.v);                                   // v = A z
             vec(launch_x_update);
             spmv_grp(c, v.x, v.ax);                                  // Ax = A x
             vec(launch_true_residual);                               // r = b - Ax
             spmv_grp(c, v.r, v.w);                                   // w = A r
-            vec_dots(launch_dots5, 5, PH_RECUR_END);
-            group_defer(c, 5, PH_RECUR_END);
+            vec_dots(launch_dots5, 5, PH_RECUR_END, DOT_DEFER);
             spmv_grp(c, v.w, v.t);                                   // t = A w
         }
-        group_flush(c);
+        c->dots.flush();
     }
 
     void iterate(int it, bool force_replace = false, bool last = true)
@@ -793,8 +584,7 @@ struct Driver {
     double drift()
     {
         spmv_grp(c, v.x, v.ax);
-        vec_dots(launch_drift, 2, PH_NONE);
-        group_now(c, 2, PH_NONE);
+        vec_dots(launch_drift, 2, PH_NONE, DOT_NOW);
         fetch_scal(c);
         return c->hS->red[1] > 0.0 ? sqrt(c->hS->red[0] / c->hS->red[1]) : 0.0;
     }
@@ -803,17 +593,14 @@ struct Driver {
 // a fresh scalar block and ticket counters for a stand-alone kernel (bicg_spmv, bicg_dot, the form probe)
 void scal_reset(bicg_ctx *c)
 {
-    c->wave_mode = false;
-    c->grp = bicg_ctx::Group{};
     c->spmv_dir = 0;             // stand-alone products and dots: always the same direction, whatever ran before
-    BICG_HIP(hipMemsetAsync(c->S, 0, sizeof(Scal), c->sc));
-    BICG_HIP(hipMemsetAsync(c->counter, 0, sizeof(unsigned) * (kShards + 1) * kCounterStride, c->sc));
+    c->dots.reset(false);
 }
 bool all_ranks(Comm *comm, bool mine);
 
 void fetch_scal(bicg_ctx *c)
 {
-    if (c->wave_mode) grp_close(c);      // the host wants the scalars: finish the open group now
+    c->dots.force();                     // the host wants the scalars: finish the open wave group now
     BICG_HIP(hipMemcpyAsync(c->hS, c->S, sizeof(Scal), hipMemcpyDeviceToHost, c->sc));
     if (c->p2p || c->persist_on) BICG_HIP(hipMemcpyAsync(c->h_alarm, c->alarm, sizeof(int), hipMemcpyDeviceToHost, c->sc));
     BICG_HIP(hipStreamSynchronize(c->sc));
@@ -859,8 +646,6 @@ void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in)
     // chain at the end of the producer (memory system draining) is then the shortest path. The
     // pipelined solvers defer their groups across an SpMV (src/solver.c:363-367, 377-385): there the sums
     // are staged by that SpMV and finished by the kernel that consumes them, off the critical path.
-    c->wave_mode = kMethod[method].pipelined;
-    c->grp = bicg_ctx::Group{};
     c->f1_done = false;
     c->spmv_dir = 0;             // every solve starts in the same direction (its first product toggles this to 1 = reversed):
                                  // run-to-run bit reproducibility, also with several groups per workgroup
@@ -886,17 +671,8 @@ void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in)
         c->trace_cap = o.max_iter > 0 ? o.max_iter : 1;
         c->trace = c->own.regrow(c->trace, 4 * (size_t)c->trace_cap);
     }
-    Scal h;
-    memset(&h, 0, sizeof h);
-    h.tol2 = o.tol * o.tol;
-    h.max_iter = o.max_iter;
-    h.tr_alpha = c->trace;
-    h.tr_omega = c->trace + c->trace_cap;
-    h.tr_beta = c->trace + 2 * (size_t)c->trace_cap;
-    h.tr_dotr = c->trace + 3 * (size_t)c->trace_cap;
-    for (int i = 0; i < 2; ++i)       // both scalar blocks: the idle one must not carry `done` of an earlier solve
-        BICG_HIP(hipMemcpyAsync(c->Sbuf + i, &h, sizeof h, hipMemcpyHostToDevice, c->sc));
-    BICG_HIP(hipMemsetAsync(c->counter, 0, sizeof(unsigned) * (kShards + 1) * kCounterStride, c->sc));
+    const Scal h = scal_block(c, o);
+    c->dots.reset(kMethod[method].pipelined, &h, true);
     BICG_HIP(hipMemsetAsync(c->alarm, 0, sizeof(int), c->sc));
     if (c->waitlog) BICG_HIP(hipMemsetAsync(c->waitlog, 0, sizeof(unsigned) * 3 * kWaitCap, c->sc));
     // every work vector starts at zero: defines the reads of p, s, z, v that the reference makes
@@ -937,7 +713,7 @@ bool graph_iteration(bicg_ctx *c, Driver &d)
     const bool want = c->graph_mode == 1;
     // consumer-side finish alternates between two scalar blocks: launch arguments change from one
     // iteration to the next unless the host enqueues the collectives itself
-    if (c->wave_mode && !hosted(c)) return false;
+    if (c->dots.wave_mode && !hosted(c)) return false;
     if (!want || c->p2p || m == BICG_PIPE_BICGSTAB_RR || c->opt.rr_drift > 0.0 || c->time_kernels || c->time_sections || c->sec_exhausted ||
         !c->comm->stream_ordered()) return false;
     if (c->graph_exec[m] && c->graph_nt[m] != c->sell_nt) {     // captured with the other streaming policy
@@ -965,10 +741,32 @@ bool graph_iteration(bicg_ctx *c, Driver &d)
     return true;
 }
 
+// What every persistent launch is told besides its vectors: patience, workgroup order, and where its sequence numbers start.
+// fixed_iters: the iterations of a kernel that uses `groups` dot groups (tags, mailbox numbers) and two exchanges per iteration,
+// converged early or not -- every rank advances its numbers by the whole chunk here. 0: the pipelined kernels number hand-offs
+// and groups densely and report what they used (replacement iterations and drift checks make the count data dependent):
+// persist_account() advances the counters after the launch.
+void persist_args(bicg_ctx *c, PersistArgs &a, unsigned groups, unsigned fixed_iters)
+{
+    a.timeout_ticks = c->p2p ? c->p2p->timeout_ticks : 200000000ull;          // 2 s inside one GPU
+    static const int xcd_map = knob_x("BICG_PERSIST_XCD") ? atoi(knob_x("BICG_PERSIST_XCD")) : 1;
+    a.xcd_map = xcd_map;
+    static const int first_sleep = knob_x("BICG_PERSIST_SLEEP") ? atoi(knob_x("BICG_PERSIST_SLEEP")) : 1;
+    a.first_sleep = (unsigned)first_sleep;
+    c->persist_seq += groups * fixed_iters;
+    if (a.multi) {
+        a.halo_seq0 = c->halo_seq;
+        a.p2p = c->p2p->red_desc(c->p2p->red_seq);
+        c->halo_seq += 2u * fixed_iters; c->p2p->red_seq += groups * fixed_iters;
+        a.ring = c->halo_ring;
+        c->halo_unsynced = 0;
+    }
+}
+
 // niter iterations of pipe_bicgstab in one launch (the open dot group has been closed: fetch_scal precedes every chunk)
 bool persist_chunk(bicg_ctx *c, int niter)
 {
-    if (c->grp.active) die("internal", "persistent chunk with an open dot group");
+    if (c->dots.is_open()) die("internal", "persistent chunk with an open dot group");
     if (c->f1_done) die("internal", "persistent chunk after phase 1 of the next iteration has run");
     const bool plain = c->method == BICG_BICGSTAB;
     const bool pipe = kMethod[c->method].pipelined;
@@ -977,27 +775,12 @@ bool persist_chunk(bicg_ctx *c, int niter)
     a.v = c->v; a.S = c->S; a.alarm = c->alarm; a.niter = niter;
     a.seq0 = c->persist_seq;
     a.vseq0 = c->persist_vseq;
-    // the pipelined kernel numbers hand-offs and groups densely and reports what it used (replacement iterations and drift
-    // checks make the count data dependent): persist_account() advances the counters after the launch
-    if (!pipe) c->persist_seq += groups * (unsigned)niter;
     a.it0 = c->it;
     a.krr = c->method == BICG_PIPE_BICGSTAB_RR ? c->opt.krr : 0; a.nrr = c->opt.nrr;
     a.force_first = 0;
     a.drift_every = (pipe && c->opt.rr_drift > 0.0) ? c->opt.check_every : 0;
     a.drift_tol2 = c->opt.rr_drift * c->opt.rr_drift;
-    a.timeout_ticks = c->p2p ? c->p2p->timeout_ticks : 200000000ull;          // 2 s inside one GPU
-    static const int xcd_map = knob_x("BICG_PERSIST_XCD") ? atoi(knob_x("BICG_PERSIST_XCD")) : 1;
-    a.xcd_map = xcd_map;
-    static const int first_sleep = knob_x("BICG_PERSIST_SLEEP") ? atoi(knob_x("BICG_PERSIST_SLEEP")) : 1;
-    a.first_sleep = (unsigned)first_sleep;
-    if (a.multi) {
-        // every rank advances its exchange and group numbers by the whole chunk, converged early or not
-        a.halo_seq0 = c->halo_seq;
-        a.p2p = c->p2p->red_desc(c->p2p->red_seq);
-        if (!pipe) { c->halo_seq += 2u * (unsigned)niter; c->p2p->red_seq += groups * (unsigned)niter; }
-        a.ring = c->halo_ring;
-        c->halo_unsynced = 0;
-    }
+    persist_args(c, a, groups, pipe ? 0u : (unsigned)niter);
     if (a.multi) {
         if (!c->waitlog) { c->waitlog = c->own.alloc<unsigned>(3 * (size_t)kWaitCap); BICG_HIP(hipMemsetAsync(c->waitlog, 0, sizeof(unsigned) * 3 * kWaitCap, c->sc)); }
         a.waitlog = c->waitlog; a.waitcap = kWaitCap;
@@ -1184,7 +967,7 @@ void probe_pipe_form(bicg_ctx *c, int method, const bicg_options *opt_in)
         scal_reset(c);
         BICG_HIP(hipMemcpyAsync(c->v.p, ones.data(), sizeof(double) * n, hipMemcpyHostToDevice, c->sc));
         c->time_kernels = false;
-        spmv(c, c->v.p, c->v.s, 0, nullptr, c->red(0, PH_NONE));
+        spmv(c, c->v.p, c->v.s, 0, nullptr, c->dots.no_dots());
         BICG_HIP(hipMemcpyAsync(bsyn, c->v.s, sizeof(double) * n, hipMemcpyDeviceToDevice, c->sc));
         BICG_HIP(hipStreamSynchronize(c->sc));
     }

@@ -71,7 +71,7 @@ EXPORTS = [
     "bicg_comm_init_single", "bicg_comm_finalize", "bicg_comm_selftest_rccl", "bicg_comm_rccl_loadable", "bicg_comm_last_error", "bicg_section_times", "bicg_comm_rank", "bicg_comm_size",
     "bicg_default_options", "bicg_create", "bicg_destroy", "bicg_solve", "bicg_load", "bicg_run", "bicg_fetch",
     "bicg_run_begin", "bicg_run_iterate", "bicg_run_iterate_timed", "bicg_run_end", "bicg_sync", "bicg_trace", "bicg_spmv", "bicg_dot", "bicg_spmv_bench", "bicg_plan_info", "bicg_ctx_flags", "bicg_spmm", "bicg_device_matrix_bytes", "bicg_uniform_entries", "bicg_constant_entries", "bicg_masked_rows", "bicg_stencil_info", "bicg_stencil_rows_per_lane", "bicg_comm_wait_stats", "bicg_plan_collisions", "bicg_product_kernels", "bicg_spmv_matrix_bytes", "bicg_last_shifted_persistent", "bicg_last_spmm_windowed", "bicg_dropin_context", "bicg_dropin_release", "bicg_dropin_stats",
-    "bicg_mtx_load_block", "bicg_mtx_free", "bicg_partition", "bicg_halo_plan", "bicg_halo_send_counts", "bicg_halo_send_lists", "bicg_row_blocks", "bicg_window_plan", "bicg_window_slot", "bicg_version", "bicg_has_experiments", "bicg_switch_value", "bicg_switch_unknown", "bicg_stream_bench", "bicg_create_device_csr", "bicg_stencil7_device", "bicg_device_free", "bicg_persist_plan", "bicg_set_plan_threads", "bicg_sell_plan_digest", "bicg_spmv_launch_plan",
+    "bicg_mtx_load_block", "bicg_mtx_free", "bicg_partition", "bicg_halo_plan", "bicg_halo_send_counts", "bicg_halo_send_lists", "bicg_row_blocks", "bicg_window_plan", "bicg_window_slot", "bicg_version", "bicg_has_experiments", "bicg_switch_value", "bicg_switch_unknown", "bicg_stream_bench", "bicg_create_device_csr", "bicg_stencil7_device", "bicg_device_free", "bicg_persist_plan", "bicg_set_plan_threads", "bicg_sell_plan_digest", "bicg_spmv_launch_plan", "bicg_dot_group_plan",
     "bicg_reorder_plan", "bicg_permute_block", "bicg_reorder_info",
     "bicg_solve_multi", "bicg_multi_trace", "bicg_comm_counts", "bicg_device_allocations",
     "bicg_update_values", "bicg_update_values_device", "bicg_persist_plan_sources", "bicg_dropin_refreshes",
@@ -1009,6 +1009,40 @@ def spmv_launch_plan(shape: dict, call: dict):
     plan = dict(zip(SPMV_PLAN, (int(v) for v in pl)))
     n = len(SPMV_STEP)
     return plan, [dict(zip(SPMV_STEP, (int(v) for v in st[i * n:(i + 1) * n]))) for i in range(plan["nsteps"])]
+
+
+# bicg_dot_group_plan (include/bicgstab_hip.h section 5): names of the entries of its four arrays, and of their values
+DOT_SHAPE = ("transport", "stream_ordered", "overlap", "inline_apply", "tail_finish", "graph_replay", "handover")
+DOT_CALL = ("regime", "n", "off", "phase", "apply_single", "event", "open", "by_product")
+DOT_PLAN = ("error", "wave", "hand", "apply_now", "n_collect", "tail", "mailbox", "deferred", "nsteps")
+DOT_STEP = ("op", "when", "stream", "roles", "n", "off", "phase")
+DOT_REGIMES = ("ticket", "wave", "hand")
+DOT_EVENTS = ("now", "defer", "force", "consume", "contribute")
+DOT_OPEN = ("none", "open", "deferred", "staged")
+DOT_OPS = ("nothing", "finish", "allreduce", "apply", "apply_p2p", "record", "wait", "stage", "consumer")
+DOT_WHEN = ("at_close", "behind_halo", "after_product", "in_consumer")
+DOT_STREAMS = ("compute", "comm")
+DOT_ROLES = {"shards": 1, "push": 2, "apply": 4, "block0": 8, "local": 16, "hand": 32}      # FIN_* (csrc/bicg_device.h)
+
+
+def dot_group_plan(shape: dict, call: dict):
+    """Who closes a dot group (bicg_dot_group_plan; no GPU, no context): shape keyed by DOT_SHAPE, call by DOT_CALL (missing
+    entries: 0; apply_single: 1) -> (plan dict keyed by DOT_PLAN, list of step dicts keyed by DOT_STEP, in order)."""
+    L = lib()
+    _ip_ = C.POINTER(C.c_int)
+    L.bicg_dot_group_plan.argtypes = [_ip_, _ip_, _ip_, _ip_]
+    L.bicg_dot_group_plan.restype = C.c_int
+    unknown = (set(shape) - set(DOT_SHAPE)) | (set(call) - set(DOT_CALL))
+    if unknown:
+        raise KeyError(f"not an entry of the shape / the call: {sorted(unknown)}")
+    sh = (C.c_int * len(DOT_SHAPE))(*(int(shape.get(k, 0)) for k in DOT_SHAPE))
+    ca = (C.c_int * len(DOT_CALL))(*(int(call.get(k, 1 if k == "apply_single" else 0)) for k in DOT_CALL))
+    pl, st = (C.c_int * len(DOT_PLAN))(), (C.c_int * (7 * len(DOT_STEP)))()
+    if L.bicg_dot_group_plan(sh, ca, pl, st) != 0:
+        raise RuntimeError("bicg_dot_group_plan failed")
+    plan = dict(zip(DOT_PLAN, (int(v) for v in pl)))
+    n = len(DOT_STEP)
+    return plan, [dict(zip(DOT_STEP, (int(v) for v in st[i * n:(i + 1) * n]))) for i in range(plan["nsteps"])]
 
 
 # bicg_reorder_plan (include/bicgstab_hip.h section 5): names of its stats

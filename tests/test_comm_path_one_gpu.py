@@ -111,6 +111,60 @@ def test_forced_comm_peer_to_peer_one_rank(problem, monkeypatch):
         H.lib().bicg_comm_init_single(0)
 
 
+def _regime_sequence(A, b, fresh):
+    """wave groups, a stand-alone dot, tickets / hand-over, a deferred ticket group, a product without dots, wave groups with
+    replacement steps, CA's two-producer group, tickets again -- on ONE context, or (fresh) every call on a context of its own"""
+    x1 = 1.0 + 1e-3 * np.arange(A.rows)
+    sigma = 0.01 * (np.arange(4) + 1.0)
+    sol = lambda r: (r["k"], r["x"].copy(), r["r"].copy())
+    calls = [lambda c: sol(c.solve("pipe_bicgstab", b, tol=1e-9, check_every=5)),
+             lambda c: c.dot(x1, b),
+             lambda c: sol(c.solve("bicgstab", b, tol=1e-15, check_every=5)),
+             lambda c: sol(c.solve_shifted(b, sigma, 1, which="shifted_pipe_lopbicgstab", tol=1e-11, check_every=5)),
+             lambda c: c.spmv(x1).copy(),
+             lambda c: sol(c.solve("pipe_bicgstab_rr", b, tol=1e-15, krr=10, nrr=3, check_every=5)),
+             lambda c: sol(c.solve("ca_bicgstab", b, tol=1e-15, check_every=5)),
+             lambda c: sol(c.solve("bicgstab", b, tol=1e-15, check_every=5))]
+    out, ctx = [], None
+    for call in calls:
+        if fresh or ctx is None:
+            ctx = H.Context(H.single_rank_blocks(A))
+        out.append(call(ctx))
+        if fresh:
+            ctx.close()
+    if not fresh:
+        ctx.close()
+    return out
+
+
+@pytest.mark.parametrize("path", ["single", "forced-comm-overlap-0", "forced-comm-overlap-1", "peer-to-peer"])
+def test_nothing_is_left_behind_between_regimes(problem, path, monkeypatch):
+    """The three dot-group regimes and the stand-alone calls one after the other on one context: each result is, bit for bit, that
+    of the same call on a fresh context -- whatever a solve leaves in the group bookkeeping, the counters, the scalar blocks or
+    the pending list does not reach the next call. 20 011 rows = 79 row groups: shard sums above and below kShards."""
+    A, b, _ = problem
+    H.lib().bicg_comm_init_single(0)
+    H.switches(persist=0, fuse_pipe=0, force_comm=None if path == "single" else 1)
+    monkeypatch.setenv("BICG_GRAPH", "0")
+    if path.startswith("forced-comm"):
+        monkeypatch.setenv("BICG_OVERLAP", path[-1])
+    try:
+        if path == "peer-to-peer":
+            buf = (C.c_char * 128)()
+            H.lib().bicg_comm_unique_id(buf)
+            H.lib().bicg_comm_init_rccl(0, 1, buf.raw, 0)
+            assert H.lib().bicg_comm_enable_p2p() == 0 and H.lib().bicg_comm_p2p_active() > 0
+        one, fresh = _regime_sequence(A, b, False), _regime_sequence(A, b, True)
+    finally:
+        H.switches(persist=None, fuse_pipe=None, force_comm=None)
+        H.lib().bicg_comm_init_single(0)
+    for i, (got, want) in enumerate(zip(one, fresh)):
+        if isinstance(want, tuple):
+            assert got[0] == want[0] and np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2]), (path, i)
+        else:
+            assert np.array_equal(got, want), (path, i)
+
+
 def test_fused_pipelined_iteration_matches_separate_kernels(problem):
     """k_spmv_sell_epi (phases in the SpMV epilogues) against the four-kernel iteration: same iteration count, same
     solution to rounding (only the association of the dot sums differs)"""
