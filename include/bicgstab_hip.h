@@ -84,6 +84,10 @@ int jacobi_bicgstab(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix 
  * drop-in context by every call. A block that cannot be inverted prints "Error: matrix has a singular diagonal block." to stderr
  * and exit(1); a bs outside 1..16 prints "Error: block size <bs> is outside 1..16." and exit(1). */
 int block_jacobi_bicgstab(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix *A_info, double *x_loc, double *r_loc, int bs);
+/* Not in the reference: BiCGStab(2) (BICG_BICGSTAB2, section 3), for matrices on which bicgstab() stagnates or breaks down -- strong
+ * convection, eigenvalues with large imaginary parts. bicgstab()'s arguments, printed lines, environment overrides and resident
+ * context; the return value and the progress lines count BiCG steps (two products each, bicgstab()'s unit), two per sweep. */
+int bicgstab2(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix *A_info, double *x_loc, double *r_loc);
 
 /* Shifted systems (A + sigma_j I) x_j = b, j = 0..sigma_len-1, solved with ONE Krylov recurrence on
  * the seed system (2 SpMV per iteration whatever the number of shifts) -- all six entry points of
@@ -178,7 +182,49 @@ typedef struct bicg_ctx bicg_ctx;
 
 enum { BICG_BICGSTAB = 0, BICG_CA_BICGSTAB = 1, BICG_PIPE_BICGSTAB = 2, BICG_PIPE_BICGSTAB_RR = 3,
        BICG_BICGSTAB_DIAG = 4,  /* BICG_BICGSTAB right-preconditioned with the diagonal of bicg_precond_diagonal (below) */
-       BICG_BICGSTAB_BLOCK = 5  /* BICG_BICGSTAB right-preconditioned with the block diagonal of bicg_precond_block_diagonal (below) */ };
+       BICG_BICGSTAB_BLOCK = 5, /* BICG_BICGSTAB right-preconditioned with the block diagonal of bicg_precond_block_diagonal (below) */
+       BICG_BICGSTAB2 = 6       /* BiCGStab(2): two BiCG steps and a two-dimensional minimal-residual step per sweep (below) */ };
+
+/* BICG_BICGSTAB2 -- Sleijpen-Fokkema BiCGStab(l) with l = 2. BICG_BICGSTAB's stabilising step minimises the
+ * residual over ONE direction and degenerates (omega -> 0) when A has eigenvalues with large imaginary parts, which is what a
+ * convection term does; this method minimises over two, by the 2 x 2 normal equations. r# is the shadow residual, r0 the residual:
+ *
+ *   set-up : r0 = b - A x0 ; r# = r0 ; u0 = u1 = u2 = 0 ; rho0 = 1, alpha = 0, omega = 1
+ *            dot_zero = dot_r = (r0,r0) ; rho1 = (r#,r0)
+ *   sweep  : rho0 = -omega rho0
+ *     j=0  : beta = alpha (rho1 / rho0) ; rho0 = rho1 ; u0 = r0 - beta u0
+ *            u1 = A u0 , (r#,u1)                         -> alpha = rho0 / (r#,u1)
+ *            x += alpha u0 ; r0 -= alpha u1
+ *            r1 = A r0 , (r#,r1)                         -> rho1
+ *     j=1  : beta = alpha (rho1 / rho0) ; rho0 = rho1 ; u0 = r0 - beta u0 ; u1 = r1 - beta u1
+ *            u2 = A u1 , (r#,u2)                         -> alpha = rho0 / (r#,u2)
+ *            x += alpha u0 ; r0 -= alpha u1 ; r1 -= alpha u2
+ *            r2 = A r1
+ *     MR   : a11 = (r1,r1), a12 = (r1,r2), a22 = (r2,r2), b1 = (r0,r1), b2 = (r0,r2)
+ *            det = a11 a22 - a12 a12 ; g1 = (b1 a22 - b2 a12) / det ; g2 = (a11 b2 - a12 b1) / det
+ *            x += g1 r0 + g2 r1 ; r0 -= g1 r1 + g2 r2 ; u0 -= g1 u1 + g2 u2 ; omega = g2
+ *            dot_r = (r0,r0) ; rho1 = (r#,r0) ; k += 2
+ *
+ * Every update is evaluated term by term from the left, one multiply and one add each, whatever the grid or the rank count; only the
+ * association of the dot sums depends on them. Options and result fields keep their meaning:
+ *   k            counts BiCG steps -- BICG_BICGSTAB's unit, one step = two products -- and advances by 2 per sweep.
+ *   loop         a further sweep runs while dot_r > tol^2 dot_zero && k + 2 <= max_iter, evaluated on the device: k never exceeds
+ *                max_iter (an odd max_iter = 7 ends at k <= 6; max_iter < 2 runs no sweep and returns k = 0 with x = x0).
+ *   steps        bicg_run_iterate(n) enqueues ceil(n / 2) sweeps; check_every counts steps the same way. Sweeps enqueued behind a
+ *                stopped solve change neither x, r nor any scalar.
+ *   result       r comes back as the recursive residual; iterations, dot_r, dot_zero and the time fields as for BICG_BICGSTAB; the
+ *                progress line is printed whenever k is a multiple of out_iter.
+ *   breakdown    a non-finite alpha, beta, g1, g2 or dot_r ends the solve; breakdown_iteration is the k of the sweep it happened in
+ *                (a 1 x 1 system ends this way in its first sweep). Nothing smarter is attempted.
+ *   trace        entries k-2 and k-1 of a sweep hold the alpha and beta of its steps j = 0 and j = 1; omega[k-2] = g1 and
+ *                omega[k-1] = g2; both dot_r entries hold the sweep's final (r0,r0), as does the history behind the progress lines.
+ *   accepted by  bicg_solve, bicg_run, bicg_run_begin / _iterate / _iterate_timed / _end and bicg_solve_device, on one rank or several
+ *                (collective as BICG_BICGSTAB). bicg_solve_multi / bicg_solve_multi_device return -2 for it.
+ *   launches     always the multi-launch form with the producer-side finish: four products, six element-wise passes and five dot
+ *                groups per sweep. Under BICG_GRAPH=1 it runs eagerly: the method has no captured iteration. It allocates nothing:
+ *                its nine vectors (x, r#, r0, r1, r2, u0, u1, u2, the set-up's A x0) are the context's work vectors.
+ * Out of scope: a preconditioned BiCGStab(2) (it needs hat recurrences for r0 and four more vectors), l > 2, multi-RHS sets, the
+ * persistent, hand-over and graph forms, shifted variants. */
 
 typedef struct {
     double tol;          /* relative residual tolerance, reference EPS (src/solver.c:3) */

@@ -35,10 +35,64 @@ __device__ __forceinline__ void finish_iteration(Scal *S, double alpha_used, boo
     }
 }
 
+// BiCGStab(2), the top of a sweep and its step j = 0 as far as no product is needed (include/bicgstab_hip.h, "sweep" and "j=0"):
+// rho0 = -omega rho0 ; beta = alpha (rho1 / rho0) ; rho0 = rho1. Run by the phase that ends the sweep before (or the set-up), so
+// that the sweep's first pass finds its beta.
+__device__ __forceinline__ void stab2_sweep_start(Scal *S)
+{
+    const double rho0 = (-S->omega) * S->rTr_old;
+    S->beta = S->alpha * (S->rTr / rho0);
+    S->rTr_old = S->rTr;
+}
+
 __device__ __forceinline__ void apply_phase(Scal *S, int phase, bool publish = true)
 {
     const double *d = S->red;
     switch (phase) {
+    case PH_S2_INIT:      // set-up: dot_zero = dot_r = (r0,r0) ; rho1 = (r#,r0), the same sum since r# = r0 ; rho0 = 1, alpha = 0, omega = 1
+        S->dot_r = d[0]; S->dot_zero = d[0]; S->rTr = d[0];
+        S->rTr_old = 1.0; S->alpha = 0.0; S->omega = 1.0;
+        if (!(S->dot_r > S->tol2 * S->dot_zero && 2 <= S->max_iter)) S->done = 1;
+        stab2_sweep_start(S);
+        break;
+    case PH_S2_ALPHA0:    // j = 0: alpha = rho0 / (r#,u1)
+    case PH_S2_ALPHA1: {  // j = 1: alpha = rho0 / (r#,u2)
+        S->alpha = S->rTr_old / d[0];
+        const int k = S->k + (phase == PH_S2_ALPHA1 ? 1 : 0);
+        if (publish && S->tr_dotr && k < S->max_iter) { S->tr_alpha[k] = S->alpha; S->tr_beta[k] = S->beta; }
+        break;
+    }
+    case PH_S2_BETA:      // j = 1: rho1 = (r#,r1) ; beta = alpha rho1 / rho0 ; rho0 = rho1
+        S->rTr = d[0];
+        S->beta = S->alpha * (S->rTr / S->rTr_old);
+        S->rTr_old = S->rTr;
+        break;
+    case PH_S2_MR: {      // MR: the 2 x 2 normal equations of min || r0 - g1 r1 - g2 r2 ||
+        const double a11 = d[0], b1 = d[1], a12 = d[2], a22 = d[3], b2 = d[4];
+        const double det = a11 * a22 - a12 * a12;
+        S->red[kRedG1] = (b1 * a22 - b2 * a12) / det;
+        S->omega = (a11 * b2 - a12 * b1) / det;
+        break;
+    }
+    case PH_S2_END: {     // the sweep's end: dot_r = (r0,r0) ; rho1 = (r#,r0) ; k += 2
+        const double g1 = S->red[kRedG1];
+        S->dot_r = d[0];
+        S->rTr = d[1];
+        S->k += 2;
+        const int k = S->k;
+        if (publish && S->tr_dotr && k <= S->max_iter) {
+            S->tr_omega[k - 2] = g1; S->tr_omega[k - 1] = S->omega;
+            S->tr_dotr[k - 2] = S->dot_r; S->tr_dotr[k - 1] = S->dot_r;
+        }
+        if (!(S->dot_r > S->tol2 * S->dot_zero && k + 2 <= S->max_iter)) S->done = 1;
+        // (alpha and beta are those of step j = 1; a non-finite one of step j = 0 has spread to them through r0, u0 and their sums)
+        if (!(isfinite(S->alpha) && isfinite(S->beta) && isfinite(g1) && isfinite(S->omega) && isfinite(S->dot_r))) {
+            if (!S->breakdown_k) S->breakdown_k = k;
+            S->done = 1;
+        }
+        stab2_sweep_start(S);
+        break;
+    }
     case PH_INIT:
         S->rTr = d[0]; S->dot_r = d[0]; S->dot_zero = d[0];
         S->alpha = 0.0; S->beta = 0.0; S->omega = 0.0; S->rTr_old = 0.0;

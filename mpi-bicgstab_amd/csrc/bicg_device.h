@@ -35,6 +35,14 @@ enum Phase : int {
     PH_OMEGA,       // red[0]=(q,y), red[1]=(y,y): omega               (src/solver.c:104, 232, 369)
     PH_PLAIN_END,   // red[0]=(r,r), red[1]=(r#,r): beta, k++          (src/solver.c:108-120)
     PH_RECUR_END,   // red[0..4]=(r,r),(r#,r),(r#,w),(r#,s),(r#,z): beta, alpha, k++ (src/solver.c:248-251, 387-390)
+    // BiCGStab(2) (Sleijpen-Fokkema, l = 2; DESIGN.md section 4.23, the sweep in include/bicgstab_hip.h): rho0 = rTr_old, rho1 = rTr,
+    // g2 = omega, g1 = red[kRedG1]. These stay below PH_SH_INIT: apply_phase_block hands that range to apply_phase
+    PH_S2_INIT,     // red[0]=(r0,r0): dot_zero = dot_r = rho1 (r# = r0), rho0 = 1, alpha = 0, omega = 1; beta of the first step
+    PH_S2_ALPHA0,   // red[0]=(r#,u1): alpha = rho0/(r#,u1), step j = 0 ; trace entry k
+    PH_S2_BETA,     // red[0]=(r#,r1): rho1 ; beta = alpha rho1/rho0 ; rho0 = rho1, step j = 1
+    PH_S2_ALPHA1,   // red[0]=(r#,u2): alpha = rho0/(r#,u2), step j = 1 ; trace entry k + 1
+    PH_S2_MR,       // red[0..4]=(r1,r1),(r0,r1),(r1,r2),(r2,r2),(r0,r2): the 2 x 2 normal equations -> g1, g2
+    PH_S2_END,      // red[0]=(r0,r0), red[1]=(r#,r0): dot_r, rho1, k += 2, loop condition, trace, breakdown ; beta of the next sweep's step j = 0
     // shifted BiCGStab (reference src/shifted_solver.c:182-354): applied by a whole workgroup,
     // one thread per shift for the per-shift scalar recurrences
     PH_SH_INIT,     // red[0]=(r,r): rTr = dot_r = dot_zero, per-shift scalars reset            (:238-255)
@@ -108,6 +116,9 @@ struct Scal {
 constexpr int kRedUsedV = 5;     // hand-offs (image tags, halo exchange numbers)
 constexpr int kRedUsedG = 6;     // dot groups (table tags, mailbox numbers)
 constexpr int kRedAdaptive = 7;  // replacement iterations the in-kernel drift check asked for
+// BiCGStab(2) never takes a persistent launch and its groups end at red[4]: g1 of the sweep's minimal-residual part lives in the first of
+// those slots from PH_S2_MR until the sweep's last element-wise pass and PH_S2_END have read it (no all-reduce covers it)
+constexpr int kRedG1 = 5;
 
 // Direct peer-to-peer transport (bicg_p2p.cpp). Values travel as "LL" words -- 8 bytes holding 32
 // payload bits and the 32-bit sequence number of the operation, written with ONE store into
@@ -750,6 +761,15 @@ void launch_dot(const double *x, const double *y, uint32_t n, Scal *S, Reduce re
 unsigned vec_grid(uint32_t n);        // workgroups used by the element-wise kernels for length n
 void set_vec_grid_cap(unsigned cap);  // ranks sharing one GPU (tests): fewer workgroups per launch (0 = default)
 void preload_vec_kernels();
+// bicg_stab2.hip
+// the element-wise passes of a BiCGStab(2) sweep, functors on bicg_vec.h's k_vec / run_vec. Vecs as Driver::iter_stab2
+// maps them: r0 = v.r, r# = v.rh, u0 = v.p, u1 = v.s, u2 = v.z, r1 = v.y, r2 = v.w
+void launch_stab2_u0(const Vecs &v, const Launch &L);                  // V1: u0 = r0 - beta u0
+void launch_stab2_r0(const Vecs &v, const Launch &L);                  // V2: r0 -= alpha u1
+void launch_stab2_xu(const Vecs &v, const Launch &L);                  // V3: x += alpha u0 ; u0 = r0 - beta u0 ; u1 = r1 - beta u1
+void launch_stab2_xrr(const Vecs &v, const Launch &L, Reduce red);     // V4: x += alpha u0 ; r0 -= alpha u1 ; r1 -= alpha u2 ; (r1,r1), (r0,r1)
+void launch_stab2_dot(const Vecs &v, const Launch &L, Reduce red);     // D:  (r0,r2)
+void launch_stab2_mr(const Vecs &v, const Launch &L, Reduce red);      // V5: x, r0, u0 of the minimal-residual part ; (r0,r0), (r#,r0)
 
 // device-side sliced-ELL plan (bicg_plan_device.hip): slice lengths + "some column is further than 32767 from its row",
 // then the column-major padded copy (32-bit columns or packed 16-bit offsets)

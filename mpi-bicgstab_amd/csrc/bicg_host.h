@@ -132,9 +132,10 @@ constexpr MethodInfo kMethod[] = {
     {11, true, Precond::NONE, true},         // BICG_PIPE_BICGSTAB_RR
     {9, false, Precond::DIAGONAL, false},    // BICG_BICGSTAB_DIAG: the plain one's six, two hat vectors, 1 / d
     {8, false, Precond::BLOCK, false},       // BICG_BICGSTAB_BLOCK: ... and the bs planes, which run_begin adds
+    {9, false, Precond::NONE, false},        // BICG_BICGSTAB2: x, r#, r0, r1, r2, u0, u1, u2 and the set-up's Ax; multi-launch form only
 };
 constexpr int kMethods = (int)(sizeof kMethod / sizeof kMethod[0]);
-static_assert(BICG_BICGSTAB == 0 && BICG_BICGSTAB_BLOCK == kMethods - 1, "kMethod follows the method enum");
+static_assert(BICG_BICGSTAB == 0 && BICG_BICGSTAB2 == kMethods - 1, "kMethod follows the method enum");
 inline Precond::Kind precond_kind_of(int method) { return method >= 0 && method < kMethods ? kMethod[method].precond : Precond::NONE; }
 
 // The dot groups of a context (bicg_dots.cpp): every buffer, counter, event and piece of bookkeeping of the

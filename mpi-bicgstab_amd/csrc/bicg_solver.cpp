@@ -453,6 +453,11 @@ struct Driver {
         const bool rr = method == BICG_PIPE_BICGSTAB_RR || (method == BICG_PIPE_BICGSTAB && c->opt.rr_drift > 0.0);
         if (!c->dots.wave_mode) {
             spmv(c, v.x, v.ax, 0, nullptr, c->dots.no_dots());                       // Ax = A x0
+            if (method == BICG_BICGSTAB2) {      // the plain set-up without p, and rho1 = (r#,r0): seeded from (r0,r0), since r# = r0 here
+                launch_init_residual(v, false, false, here(), c->dots.open(1, PH_S2_INIT));
+                c->dots.close();
+                return;
+            }
             // r = b - Ax, r# = r, (r,r); the plain iterations: p = r; DIAGONAL: and p^ = dinv o p in the same pass
             if (hat == Precond::DIAGONAL) launch_init_residual_diag(v, c->pc.planes, here(), c->dots.open(1, PH_INIT));
             else launch_init_residual(v, plain, rr, here(), c->dots.open(1, PH_INIT));
@@ -505,6 +510,28 @@ struct Driver {
         if (hat == Precond::DIAGONAL) launch_diag_p(v, dinv, here());   // p = r + beta (p - omega s) ; p^ = dinv o p
         else launch_plain_p(v, here());
         if (hat == Precond::BLOCK) precond_apply(c, v.p, v.z);          // p^ = M^-1 p
+    }
+
+    // One sweep of BiCGStab(2) = two BiCG steps and the two-dimensional minimal-residual step (the algorithm: include/bicgstab_hip.h at
+    // BICG_BICGSTAB2; launches, dot groups and bytes per row: DESIGN.md section 4.23). The vectors live in the slab's work vectors, all
+    // zeroed with their halo tails by run_begin, which defines u0 = u1 = u2 = 0:
+    //   r0 = v.r   r# = v.rh   u0 = v.p   u1 = v.s   u2 = v.z   r1 = v.y   r2 = v.w   (the set-up's A x0: v.ax; idle: v.v, v.t, v.b)
+    // rho0 / rho1 are Scal::rTr_old / rTr, g2 is Scal::omega, g1 sits in Scal::red[kRedG1]. Ten launches, five dot groups:
+    // the three products with (r#, out) close a group each, the MR group's five sums come from three producers -- V4 and the product
+    // r2 = A r1 contribute, the dot pass closes --, and V5 closes the sweep's last one. Always ticket groups, producer-side finish.
+    void iter_stab2()
+    {
+        DotGroups &d = c->dots;
+        launch_stab2_u0(v, here());                                             // V1: u0 = r0 - beta u0
+        spmv(c, v.p, v.s, 1, v.rh, d.open(1, PH_S2_ALPHA0)); d.close();         // u1 = A u0, (r#,u1) -> alpha
+        launch_stab2_r0(v, here());                                             // V2: r0 -= alpha u1
+        spmv(c, v.r, v.y, 1, v.rh, d.open(1, PH_S2_BETA)); d.close();           // r1 = A r0, (r#,r1) -> rho1, beta
+        launch_stab2_xu(v, here());                                             // V3: x += alpha u0 (j = 0) ; u0 = r0 - beta u0 ; u1 = r1 - beta u1
+        spmv(c, v.s, v.z, 1, v.rh, d.open(1, PH_S2_ALPHA1)); d.close();         // u2 = A u1, (r#,u2) -> alpha
+        launch_stab2_xrr(v, here(), d.contribute(0, false));                    // V4: x, r0, r1 ; (r1,r1), (r0,r1) -> red[0], red[1]
+        spmv(c, v.y, v.w, 2, v.y, d.contribute(2, false));                      // r2 = A r1, (r1,r2), (r2,r2) -> red[2], red[3]
+        launch_stab2_dot(v, here(), d.open(5, PH_S2_MR, DOT_NOW, 4)); d.close();   // D: (r0,r2) -> red[4] ; the five -> g1, g2
+        launch_stab2_mr(v, here(), d.open(2, PH_S2_END)); d.close();            // V5: x, r0, u0 ; (r0,r0), (r#,r0) -> dot_r, rho1, k += 2
     }
 
     void iter_ca()      // reference src/solver.c:217-251
@@ -576,6 +603,7 @@ struct Driver {
         switch (method) {
         case BICG_BICGSTAB: case BICG_BICGSTAB_DIAG: case BICG_BICGSTAB_BLOCK: iter_plain(); break;
         case BICG_CA_BICGSTAB: iter_ca(); break;
+        case BICG_BICGSTAB2: iter_stab2(); break;
         default: iter_pipe(it, force_replace, last); break;
         }
     }
@@ -710,7 +738,7 @@ bool graph_iteration(bicg_ctx *c, Driver &d)
     // Off unless BICG_GRAPH=1: measured on one MI355X, eager in-order enqueueing already keeps the
     // GPU busy (54 us vs 60 us replayed per 17-op iteration of a 200 k-row rank); replay only pays
     // when the two-stream overlap mode is on (80 vs 105 us).
-    const bool want = c->graph_mode == 1;
+    const bool want = c->graph_mode == 1 && m != BICG_BICGSTAB2;      // (BiCGStab(2) has no captured iteration: it runs eagerly)
     // consumer-side finish alternates between two scalar blocks: launch arguments change from one
     // iteration to the next unless the host enqueues the collectives itself
     if (c->dots.wave_mode && !hosted(c)) return false;
@@ -866,13 +894,20 @@ int run_iterate(bicg_ctx *c, int nsteps)
         sec_mark(c, SEC_VEC);
         const double t_chunk = now_sec();
         if (persist) persist = persist_chunk(c, chunk);   // one launch for the whole chunk (bicg_persist.hip); false: it could not be launched
-        for (int j = 0; j < chunk && !persist; ++j) {
-            // the last iteration before the caller (or the drift check) reads x / r leaves them as the reference would
-            const bool last = j == chunk - 1 && (c->it + chunk >= stop || o.rr_drift > 0.0);
-            if (j == 0 && force) { d.iterate(c->it, true, last); continue; }
-            if (!graph_iteration(c, d)) d.iterate(c->it + j, false, last);
+        int steps = chunk;      // what the chunk advances c->it by
+        if (c->method == BICG_BICGSTAB2) {      // steps come in pairs: ceil(chunk / 2) sweeps (the device's loop condition keeps k <= max_iter)
+            const int sweeps = (chunk + 1) / 2;
+            for (int j = 0; j < sweeps; ++j) d.iterate(c->it + 2 * j, false, j == sweeps - 1);
+            steps = 2 * sweeps;
+        } else if (!persist) {
+            for (int j = 0; j < chunk; ++j) {
+                // the last iteration before the caller (or the drift check) reads x / r leaves them as the reference would
+                const bool last = j == chunk - 1 && (c->it + chunk >= stop || o.rr_drift > 0.0);
+                if (j == 0 && force) { d.iterate(c->it, true, last); continue; }
+                if (!graph_iteration(c, d)) d.iterate(c->it + j, false, last);
+            }
         }
-        c->it += chunk;
+        c->it += steps;
         sec_mark(c, SEC_STOP);
         c->t_enq += now_sec() - t_chunk;          // (bicg_run_iterate_timed: host time until the chunk's launches were enqueued)
         fetch_scal(c);

@@ -28,7 +28,8 @@ class _Methods(dict):
 
 
 METHODS = _Methods({"bicgstab": 0, "ca_bicgstab": 1, "pipe_bicgstab": 2, "pipe_bicgstab_rr": 3, "bicgstab_diag": 4})
-LATER_METHODS = {"bicgstab_block": 5}      # BICG_BICGSTAB_BLOCK
+LATER_METHODS = {"bicgstab_block": 5,      # BICG_BICGSTAB_BLOCK
+                 "bicgstab2": 6}           # BICG_BICGSTAB2
 
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
@@ -201,7 +202,7 @@ def lib():
         for fn in (L.bicg_precond_block_diagonal, L.bicg_precond_block_diagonal_device, L.bicg_precond_apply, L.bicg_csr_block_diagonal,
                    L.block_jacobi_bicgstab):
             fn.restype = C.c_int
-        for name in ("bicgstab", "ca_bicgstab", "pipe_bicgstab", "jacobi_bicgstab"):
+        for name in ("bicgstab", "ca_bicgstab", "pipe_bicgstab", "jacobi_bicgstab", "bicgstab2"):
             getattr(L, name).argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp]
         L.pipe_bicgstab_rr.argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp,
                                        C.c_int, C.c_int]
