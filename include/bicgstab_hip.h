@@ -427,9 +427,11 @@ int bicg_shifted_residuals(bicg_ctx *ctx, const double *x_loc_set, const double 
 /* "Batched SpMV" (BASELINE.json configs[4]): Y_j = (A + sigma_j I) X_j for nvec vectors with every matrix entry read once
  * per 16 vectors (sliced-ELL SpMM) -- what the loop above does internally. x_loc_set / y_loc_set are shift-major like
  * x_loc_set of the shifted solvers; sigma may be NULL (Y_j = A X_j). Every column is bit-identical to bicg_spmv of that
- * vector. Padded and jagged slices, x-window slots and lane-permuted groups are all read (BICG_FLAG_SPMM); returns 1 without
- * computing only when some rows are on the CSR / rows-over-lanes kernels (a row several times longer than the average). ms_device
- * (optional) receives the device time of the passes (halo exchanges, layout change and SpMM kernel). Collective. */
+ * vector. Padded and jagged slices, x-window slots and lane-permuted groups are all read (BICG_FLAG_SPMM). Where some rows are on
+ * the CSR / rows-over-lanes kernels (a row several times longer than the average) there is no SpMM kernel: the columns are
+ * multiplied one by one by bicg_spmv's kernels with the shift in their epilogue, A is read nvec times and ms_device receives 0.
+ * ms_device (optional) otherwise receives the device time of the passes (halo exchanges, layout change and SpMM kernel).
+ * Collective. */
 int bicg_spmm(bicg_ctx *ctx, const double *x_loc_set, const double *sigma, int nvec, double *y_loc_set, double *ms_device);
 /* per-iteration trace of the last run (record_trace): arrays of length >= iterations, may be NULL */
 int bicg_trace(bicg_ctx *ctx, double *alpha, double *omega, double *beta, double *dot_r);

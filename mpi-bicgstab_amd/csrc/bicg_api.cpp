@@ -283,17 +283,32 @@ int bicg_shifted_residuals(bicg_ctx *c, const double *x_loc_set, const double *b
 }
 
 // Y_j = (A + sigma_j I) X_j, j < nvec, with A read once per kSpmmCols vectors ("batched SpMV", BASELINE.json configs[4]);
-// x_loc_set / y_loc_set shift-major like the shifted solvers' x_loc_set; sigma may be NULL. Returns 1 (nothing done)
-// when the matrix is not entirely on the sliced-ELL path. ms_out (optional): device time of the passes.
+// x_loc_set / y_loc_set shift-major like the shifted solvers' x_loc_set; sigma may be NULL. A block that is not entirely on the
+// sliced-ELL path has no SpMM kernel: its columns are multiplied one by one (A read nvec times, *ms_out = 0). Returns 0.
+// ms_out (optional): device time of the passes.
 int bicg_spmm(bicg_ctx *c, const double *x_loc_set, const double *sigma, int nvec, double *y_loc_set, double *ms_out)
 {
     use_device(c);
-    if (!c->spmm_ok) return 1;
     reset_scal(c);
-    spmm_buffers(c);
     std::vector<double> ph_y;
     if (c->phantom) { x_loc_set = host_in(c, x_loc_set, (size_t)nvec); ph_y.assign((size_t)nvec, 0.0); y_loc_set = ph_y.data(); }
     const size_t n = c->n_loc;
+    if (!c->spmm_ok) {
+        // no SpMM kernel for this block (CSR row blocks, rows over lanes): one product per vector with the shift in its
+        // epilogue, as in bicg_shifted_residuals -- every column is bicg_spmv's, then + sigma_j x_j. No device time is reported.
+        c->time_kernels = false;
+        for (int j = 0; j < nvec; ++j) {
+            vec_upload(c, c->v.p, c->stride, x_loc_set + (size_t)j * n, 1, true);
+            c->cur_shift = sigma ? sigma[j] : 0.0; c->cur_has_shift = sigma != nullptr;
+            spmv(c, c->v.p, c->v.ax, 0, nullptr, c->dots.no_dots());
+            c->cur_has_shift = false; c->cur_shift = 0.0;
+            vec_download(c, y_loc_set + (size_t)j * n, c->v.ax, c->stride, 1, true);
+            fetch_scal(c);
+        }
+        if (ms_out) *ms_out = 0.0;
+        return 0;
+    }
+    spmm_buffers(c);
     hipEvent_t e0, e1;
     BICG_HIP(hipEventCreate(&e0)); BICG_HIP(hipEventCreate(&e1));
     float total = 0.f;

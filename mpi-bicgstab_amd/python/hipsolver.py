@@ -651,14 +651,15 @@ class Context:
         return out
 
     def spmm(self, x_set, sigma=None):
-        """Y_j = (A + sigma_j I) X_j for all rows of x_set [nvec][n], A read once per 16 vectors -> (Y, device ms)"""
+        """Y_j = (A + sigma_j I) X_j for all rows of x_set [nvec][n], A read once per 16 vectors -> (Y, device ms); without
+        flags()["spmm"] (CSR row blocks, rows over lanes) one product per vector and 0 ms"""
         x = np.ascontiguousarray(x_set, dtype=np.float64).reshape(-1, self.n)
         y = np.zeros_like(x)
         sg = None if sigma is None else np.ascontiguousarray(sigma, dtype=np.float64)
         ms = C.c_double(0.0)
         rc = lib().bicg_spmm(self.h, _d(x), None if sg is None else _d(sg), x.shape[0], _d(y), C.byref(ms))
         if rc != 0:
-            raise RuntimeError("bicg_spmm: the matrix is not entirely on the sliced-ELL path")
+            raise RuntimeError("bicg_spmm failed")
         return y, ms.value
 
     def load(self, x0, b, stream=None):

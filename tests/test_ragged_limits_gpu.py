@@ -21,13 +21,12 @@ A group whose rows are all empty has a zero partial by construction: `IntegerSys
 The small cases build their contexts per test; the large one (`list_limits`, 6.9 M non-zeros) has one context per value of jagw
 for the whole module, and its values are replaced in place (update_values, itself checked) where a test needs other values."""
 import functools
-from fractions import Fraction
 
 import numpy as np
 import pytest
 
-import oracle_lib as O
 import ragged_cases as R
+from bitwise import IntegerSystem, assert_same_bits, check_first_dots, oracle_spmv, same_bits
 from mpi_bicgstab_amd import hipsolver as H
 
 pytestmark = pytest.mark.gpu
@@ -54,25 +53,10 @@ def context(A, sw, jagw):
         H.switches(**{k: None for k in tokens})
 
 
-def same_bits(got, want):
-    return np.ascontiguousarray(got, dtype=np.float64).tobytes() == np.ascontiguousarray(want, dtype=np.float64).tobytes()
-
-
-def assert_same_bits(got, want, what):
-    if not same_bits(got, want):
-        bad = np.flatnonzero(np.asarray(got).view(np.uint64).ravel() != np.asarray(want).view(np.uint64).ravel())
-        raise AssertionError(f"{what}: {len(bad)} of {np.size(want)} values differ in their bits, the first at {bad[:8].tolist()}")
-
-
 def kernel_at(facts, jagw):
     """the product kernel a case runs: the three-trip one its facts name, or -- jagw=0 hands no lane words to the launch --
     k_spmv_sell's loop over the window / over the gathered slices"""
     return facts["kernel"] if jagw else ("sell_window_loop" if facts["window"] else "sell_jagged")
-
-
-def oracle_spmv(A, x):
-    row, col, val = A.to_coo()
-    return O.spmv(A.rows, row, col, val, x)
 
 
 @functools.lru_cache(maxsize=None)
@@ -96,46 +80,9 @@ def check_product(ctx, A, facts, jagw, x, want, what):
     assert same_bits(y1[empty], np.zeros(int(empty.sum()))), (what, "rows without entries give +0.0")
 
 
-class IntegerSystem:
-    """the integer values of a case, b from {1, 2, 3}, and the first iteration's exact scalars: dot_zero = (b, b) and
-    alpha_1 = (b, b) / (b, A b) (x0 = 0: r = r# = p = b). Asserts what the byte comparison rests on."""
-
-    def __init__(self, name):
-        self.A, self.facts, self.sw = R.build(name, "integer")
-        A = self.A
-        n = A.rows
-        assert set(np.unique(A.val)) <= {1.0, 2.0, 3.0}
-        row, col, _ = A.to_coo()
-        b = np.random.default_rng(2000).integers(1, 4, size=n)
-        ival = A.val.astype(np.int64)
-        terms = ival * b[col.astype(np.int64)]
-        assert int(terms.sum()) < 2 ** 53          # (so the float64 weights below add up exactly)
-        Ab = np.bincount(row.astype(np.int64), weights=terms.astype(np.float64), minlength=n).astype(np.int64)
-        self.b, self.Ab = b, Ab
-        self.bb, self.bAb = int((b * b).sum()), int((b * Ab).sum())
-        assert 0 < self.bb < 2 ** 53 and 0 < self.bAb < 2 ** 53 and int(Ab.max()) < 2 ** 26      # (all terms are positive: the sums are the absolute sums)
-        # one partial of (b, A b) per 256-row group, at the finest: none is zero, except where the group holds no entry at all
-        groups = np.arange(n) // R.GROUP
-        part = np.bincount(groups, weights=(b * Ab).astype(np.float64))
-        holds = np.bincount(row.astype(np.int64) // R.GROUP, minlength=len(part)) > 0
-        assert np.all(part[holds] > 0)
-        empty = sorted(np.flatnonzero(~holds).tolist())
-        assert empty == ([self.facts["groups"]["all_empty"]] if "groups" in self.facts else []), "only the group crafted to be empty"
-        self.dot_zero = float(self.bb)
-        self.alpha = float(Fraction(self.bb, self.bAb))
-
-
 @functools.lru_cache(maxsize=None)
 def integer_system(name):
-    return IntegerSystem(name)
-
-
-def check_first_dots(ctx, S, what):
-    got = ctx.solve("bicgstab", S.b.astype(np.float64), tol=0.0, max_iter=1, check_every=1)
-    assert got["k"] == 1, what
-    assert same_bits(got["result"].dot_zero, S.dot_zero), (what, got["result"].dot_zero, S.bb)
-    alpha = ctx.trace(1)["alpha"][0]
-    assert same_bits(alpha, S.alpha), (what, float(alpha), S.alpha, S.bb, S.bAb)
+    return IntegerSystem(name, R)
 
 
 @functools.lru_cache(maxsize=None)
