@@ -88,6 +88,12 @@ int block_jacobi_bicgstab(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_M
  * convection, eigenvalues with large imaginary parts. bicgstab()'s arguments, printed lines, environment overrides and resident
  * context; the return value and the progress lines count BiCG steps (two products each, bicgstab()'s unit), two per sweep. */
 int bicgstab2(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix *A_info, double *x_loc, double *r_loc);
+/* Not in the reference: bicgstab2() right-preconditioned with M = diag(A) (BICG_BICGSTAB2_DIAG) or with the bs x bs diagonal blocks
+ * of A (BICG_BICGSTAB2_BLOCK; section 3), for matrices that are convective and badly scaled or block-coupled. Arguments, printed lines
+ * and counting are bicgstab2()'s; the preconditioner is read from A_loc_diag and installed by every call, and the error lines and
+ * exits are those of jacobi_bicgstab() / block_jacobi_bicgstab(). */
+int jacobi_bicgstab2(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix *A_info, double *x_loc, double *r_loc);
+int block_jacobi_bicgstab2(CSR_Matrix *A_loc_diag, CSR_Matrix *A_loc_offd, INFO_Matrix *A_info, double *x_loc, double *r_loc, int bs);
 
 /* Shifted systems (A + sigma_j I) x_j = b, j = 0..sigma_len-1, solved with ONE Krylov recurrence on
  * the seed system (2 SpMV per iteration whatever the number of shifts) -- all six entry points of
@@ -183,7 +189,9 @@ typedef struct bicg_ctx bicg_ctx;
 enum { BICG_BICGSTAB = 0, BICG_CA_BICGSTAB = 1, BICG_PIPE_BICGSTAB = 2, BICG_PIPE_BICGSTAB_RR = 3,
        BICG_BICGSTAB_DIAG = 4,  /* BICG_BICGSTAB right-preconditioned with the diagonal of bicg_precond_diagonal (below) */
        BICG_BICGSTAB_BLOCK = 5, /* BICG_BICGSTAB right-preconditioned with the block diagonal of bicg_precond_block_diagonal (below) */
-       BICG_BICGSTAB2 = 6       /* BiCGStab(2): two BiCG steps and a two-dimensional minimal-residual step per sweep (below) */ };
+       BICG_BICGSTAB2 = 6,      /* BiCGStab(2): two BiCG steps and a two-dimensional minimal-residual step per sweep (below) */
+       BICG_BICGSTAB2_DIAG = 7, /* BICG_BICGSTAB2 right-preconditioned with the diagonal of bicg_precond_diagonal (below) */
+       BICG_BICGSTAB2_BLOCK = 8 /* BICG_BICGSTAB2 right-preconditioned with the block diagonal of bicg_precond_block_diagonal (below) */ };
 
 /* BICG_BICGSTAB2 -- Sleijpen-Fokkema BiCGStab(l) with l = 2. BICG_BICGSTAB's stabilising step minimises the
  * residual over ONE direction and degenerates (omega -> 0) when A has eigenvalues with large imaginary parts, which is what a
@@ -223,8 +231,49 @@ enum { BICG_BICGSTAB = 0, BICG_CA_BICGSTAB = 1, BICG_PIPE_BICGSTAB = 2, BICG_PIP
  *   launches     always the multi-launch form with the producer-side finish: four products, six element-wise passes and five dot
  *                groups per sweep. Under BICG_GRAPH=1 it runs eagerly: the method has no captured iteration. It allocates nothing:
  *                its nine vectors (x, r#, r0, r1, r2, u0, u1, u2, the set-up's A x0) are the context's work vectors.
- * Out of scope: a preconditioned BiCGStab(2) (it needs hat recurrences for r0 and four more vectors), l > 2, multi-RHS sets, the
- * persistent, hand-over and graph forms, shifted variants. */
+ * Out of scope: l > 2, multi-RHS sets, the persistent, hand-over and graph forms, shifted variants. (Preconditioned: methods 7 and 8.)
+ *
+ * BICG_BICGSTAB2_DIAG (7) and BICG_BICGSTAB2_BLOCK (8) -- the sweep above on A M^-1, right-preconditioned with the preconditioner the
+ * context holds (bicg_precond_diagonal, kind 1, for method 7; bicg_precond_block_diagonal, kind 2, for method 8; DESIGN.md section
+ * 4.24): for matrices that are convective AND badly scaled or block-coupled, on which methods 0, 4, 5 and 6 all fail. r0 stays the
+ * residual of the caller's system A x = b, so the stopping test, k, the trace, the breakdown rule, the progress lines, check_every,
+ * bicg_run_iterate(n) = ceil(n / 2) sweeps and "sweeps behind a stopped solve change neither x, r nor a scalar" are method 6's. Four
+ * hat vectors ride along, u^0, u^1, r^0, r^1:
+ *
+ *   set-up : as method 6 (r0 = b - A x0 ; r# = r0 ; u0 = u1 = u2 = 0)
+ *   sweep  : rho0 = -omega rho0
+ *     j=0  : beta ; u0 = r0 - beta u0 ;                       u^0 = M^-1 u0          [application 1]
+ *            u1 = A u^0 , (r#,u1) -> alpha
+ *            r0 -= alpha u1 ;                                 r^0 = M^-1 r0          [application 2]
+ *            r1 = A r^0 , (r#,r1) -> rho1
+ *     j=1  : beta ; x += alpha u^0 (step j = 0's) ; u0 = r0 - beta u0 ;   u^0 = r^0 - beta u^0   [recurrence]
+ *            u1 = r1 - beta u1 ;                              u^1 = M^-1 u1          [application 3]
+ *            u2 = A u^1 , (r#,u2) -> alpha
+ *            x += alpha u^0 ; r0 -= alpha u1 ;                r^0 -= alpha u^1       [recurrence]
+ *            r1 -= alpha u2 ;                                 r^1 = M^-1 r1          [application 4]
+ *            r2 = A r^1
+ *     MR   : the five sums on r0, r1, r2 as above -> g1, g2
+ *            x += g1 r^0 + g2 r^1 ; r0 -= g1 r1 + g2 r2 ; u0 -= g1 u1 + g2 u2 ; dot_r = (r0,r0) ; rho1 = (r#,r0) ; k += 2
+ *
+ * Four applications of M^-1 and two hat recurrences per sweep; the recurrences feed x alone -- every product's input is a fresh
+ * application, so the recursive residual does not depend on them. Every expression is one multiply and one add per term from the
+ * left, as above; a diagonal application is dinv_i v_i, a block application is bicg_precond_apply's. Consequences, bit for bit: with
+ * d = 1 (or identity blocks) the sweep is method 6's; method 8 with bs = 1, or with blocks that hold d on their diagonals and zeros
+ * elsewhere, is method 7 with that d (as long as no entry of a vector M^-1 is applied to is a zero, whose sign the two forms may
+ * render differently).
+ *   launches     method 7 forms the applications in the pass that produces the vector: ten launches per sweep, as method 6. Method 8
+ *                follows each of those four passes with a launch of the block application, which writes the hat vector only:
+ *                fourteen. Under BICG_GRAPH=1 both run eagerly. They allocate nothing: the hat vectors are the four work vectors
+ *                method 6 leaves idle.
+ *   accepted by  bicg_solve, bicg_run, bicg_run_begin / _iterate / _iterate_timed / _end and bicg_solve_device, on one rank or several
+ *                (collective as method 6; blocks are local to a rank). On a context whose bicg_precond_kind is not the method's (1 /
+ *                2) these calls return -2 and touch nothing. bicg_solve_multi / bicg_solve_multi_device return -2 for both.
+ *   across ranks the refusal is a rank's own, as for methods 4 and 5: no rank asks another whether it holds the preconditioner. A rank
+ *                whose preconditioner was cleared returns -2 at once and takes no part in the solve, while the ranks that hold one
+ *                enter it and wait for that rank in their first collective. Installing on every rank, or on none, is the caller's
+ *                contract.
+ * Out of scope here: forming the block application in the producing pass (it needs out-of-place r0 / u1), l > 2, multi-RHS sets, the
+ * persistent, hand-over and graph forms, CA / pipelined / shifted preconditioned forms, other preconditioner kinds. */
 
 typedef struct {
     double tol;          /* relative residual tolerance, reference EPS (src/solver.c:3) */
@@ -449,7 +498,7 @@ int bicg_trace(bicg_ctx *ctx, double *alpha, double *omega, double *beta, double
  * opt->check_every iterations are enqueued between host reads of the columns' flags; opt->record_trace keeps alpha, omega, beta
  * and (r,r) per column and iteration for bicg_multi_trace (max_iter x 16 x 4 doubles per set). res (nrhs entries, may be NULL):
  * iterations, dot_r, dot_zero and breakdown_iteration of column j; the time fields of every entry are those of the whole call.
- * Returns the largest k_j; -2 for methods 1-3, for method 4 or 5 on a context whose bicg_precond_kind is not that method's (1 / 2),
+ * Returns the largest k_j; -2 for methods 1-3 and 6-8, for method 4 or 5 on a context whose bicg_precond_kind is not that method's (1 / 2),
  * or for nrhs < 1 -- a refused call touches nothing: neither x, r, the trace nor any allocation.
  * METHODS 4 AND 5: column j runs exactly the right-preconditioned iteration bicg_solve runs for that method on (x0_j, b_j): the two
  * products take P^ = M^-1 P and Q^ = M^-1 Q, x += alpha p^ + omega q^, r stays the residual of the caller's system, and the loop

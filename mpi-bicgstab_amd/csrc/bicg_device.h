@@ -770,6 +770,14 @@ void launch_stab2_xu(const Vecs &v, const Launch &L);                  // V3: x 
 void launch_stab2_xrr(const Vecs &v, const Launch &L, Reduce red);     // V4: x += alpha u0 ; r0 -= alpha u1 ; r1 -= alpha u2 ; (r1,r1), (r0,r1)
 void launch_stab2_dot(const Vecs &v, const Launch &L, Reduce red);     // D:  (r0,r2)
 void launch_stab2_mr(const Vecs &v, const Launch &L, Reduce red);      // V5: x, r0, u0 of the minimal-residual part ; (r0,r0), (r#,r0)
+// ... and of the right-preconditioned sweep (Driver::iter_stab2_hat): the same passes carrying the hat vectors
+// u^0 = v.v, u^1 = v.t, r^0 = v.b, r^1 = v.ax. dinv: the plane of 1 / d, the application dinv o v is formed in the pass that produces
+// v; null (block Jacobi): the pass leaves the application to the launch of k_bjac_apply that follows it
+void launch_stab2h_u0(const Vecs &v, const double *dinv, const Launch &L);                // V1': V1 ; u^0 = dinv o u0
+void launch_stab2h_r0(const Vecs &v, const double *dinv, const Launch &L);                // V2': V2 ; r^0 = dinv o r0
+void launch_stab2h_xu(const Vecs &v, const double *dinv, const Launch &L);                // V3': x += alpha u^0 ; u0, u1 ; u^0 = r^0 - beta u^0 ; u^1 = dinv o u1
+void launch_stab2h_xrr(const Vecs &v, const double *dinv, const Launch &L, Reduce red);   // V4': x += alpha u^0 ; r0, r1 ; r^0 -= alpha u^1 ; r^1 = dinv o r1 ; two sums
+void launch_stab2h_mr(const Vecs &v, const Launch &L, Reduce red);                        // V5': x += g1 r^0 + g2 r^1 ; r0, u0 ; two sums
 
 // device-side sliced-ELL plan (bicg_plan_device.hip): slice lengths + "some column is further than 32767 from its row",
 // then the column-major padded copy (32-bit columns or packed 16-bit offsets)

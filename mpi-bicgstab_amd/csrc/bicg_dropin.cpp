@@ -323,6 +323,8 @@ int bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r)
 int jacobi_bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_BICGSTAB_DIAG, d, o, i, x, r, 0, 0); }
 int block_jacobi_bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r, int bs) { return dropin(BICG_BICGSTAB_BLOCK, d, o, i, x, r, 0, 0, bs); }
 int bicgstab2(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_BICGSTAB2, d, o, i, x, r, 0, 0); }      // not in the reference
+int jacobi_bicgstab2(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_BICGSTAB2_DIAG, d, o, i, x, r, 0, 0); }
+int block_jacobi_bicgstab2(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r, int bs) { return dropin(BICG_BICGSTAB2_BLOCK, d, o, i, x, r, 0, 0, bs); }
 int ca_bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_CA_BICGSTAB, d, o, i, x, r, 0, 0); }
 int pipe_bicgstab(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r) { return dropin(BICG_PIPE_BICGSTAB, d, o, i, x, r, 0, 0); }
 int pipe_bicgstab_rr(CSR_Matrix *d, CSR_Matrix *o, INFO_Matrix *i, double *x, double *r, int krr, int nrr)

@@ -124,19 +124,23 @@ struct MethodInfo {
     bool pipelined;             // dot groups deferred across a product: consumer-side finish (DotGroups::wave_mode)
     Precond::Kind precond;      // the preconditioner the method needs on the context
     bool persist;               // may take the persistent launch at all (run_iterate decides per context)
+    bool stab2;                 // BiCGStab(2) sweeps: its own set-up, steps come in pairs (run_iterate), no captured iteration
 };
 constexpr MethodInfo kMethod[] = {
-    {6, false, Precond::NONE, true},         // BICG_BICGSTAB
-    {8, false, Precond::NONE, true},         // BICG_CA_BICGSTAB
-    {10, true, Precond::NONE, true},         // BICG_PIPE_BICGSTAB
-    {11, true, Precond::NONE, true},         // BICG_PIPE_BICGSTAB_RR
-    {9, false, Precond::DIAGONAL, false},    // BICG_BICGSTAB_DIAG: the plain one's six, two hat vectors, 1 / d
-    {8, false, Precond::BLOCK, false},       // BICG_BICGSTAB_BLOCK: ... and the bs planes, which run_begin adds
-    {9, false, Precond::NONE, false},        // BICG_BICGSTAB2: x, r#, r0, r1, r2, u0, u1, u2 and the set-up's Ax; multi-launch form only
+    {6, false, Precond::NONE, true, false},         // BICG_BICGSTAB
+    {8, false, Precond::NONE, true, false},         // BICG_CA_BICGSTAB
+    {10, true, Precond::NONE, true, false},         // BICG_PIPE_BICGSTAB
+    {11, true, Precond::NONE, true, false},         // BICG_PIPE_BICGSTAB_RR
+    {9, false, Precond::DIAGONAL, false, false},    // BICG_BICGSTAB_DIAG: the plain one's six, two hat vectors, 1 / d
+    {8, false, Precond::BLOCK, false, false},       // BICG_BICGSTAB_BLOCK: ... and the bs planes, which run_begin adds
+    {9, false, Precond::NONE, false, true},         // BICG_BICGSTAB2: x, r#, r0, r1, r2, u0, u1, u2 and the set-up's Ax; multi-launch form only
+    {13, false, Precond::DIAGONAL, false, true},    // BICG_BICGSTAB2_DIAG: method 6's eight, the four hat vectors (one in Ax's place), 1 / d
+    {12, false, Precond::BLOCK, false, true},       // BICG_BICGSTAB2_BLOCK: ... and the bs planes, which run_begin adds
 };
 constexpr int kMethods = (int)(sizeof kMethod / sizeof kMethod[0]);
-static_assert(BICG_BICGSTAB == 0 && BICG_BICGSTAB2 == kMethods - 1, "kMethod follows the method enum");
+static_assert(BICG_BICGSTAB == 0 && BICG_BICGSTAB2 == 6 && BICG_BICGSTAB2_BLOCK == kMethods - 1, "kMethod follows the method enum");
 inline Precond::Kind precond_kind_of(int method) { return method >= 0 && method < kMethods ? kMethod[method].precond : Precond::NONE; }
+inline bool method_stab2(int method) { return method >= 0 && method < kMethods && kMethod[method].stab2; }
 
 // The dot groups of a context (bicg_dots.cpp): every buffer, counter, event and piece of bookkeeping of the
 // three regimes -- tickets / tail finish, consumer-side finish (wave), hand-over -- and the one interface through which the solvers

@@ -148,7 +148,7 @@ int solve_multi_any(bicg_ctx *c, int method, double *x_loc_set, double *r_loc_se
     if (device && !c->phantom && (!x_loc_set || !r_loc_set)) return -1;
     // plain BiCGStab, as it stands or right-preconditioned with the preconditioner the context holds
     const Precond::Kind hat = precond_kind_of(method);
-    if ((method != BICG_BICGSTAB && hat == Precond::NONE) || diag_refused(c, method)) return -2;
+    if ((method != BICG_BICGSTAB && hat == Precond::NONE) || method_stab2(method) || diag_refused(c, method)) return -2;      // (no BiCGStab(2) sets)
     if (nrhs < 1 || (device && !c->phantom && ld < c->n_loc)) return -2;
     use_device(c);
     std::vector<double> ph_x, ph_r;        // a context without rows holds one phantom row: zeros in, nothing out (host_in)

@@ -449,11 +449,11 @@ struct Driver {
 
     void init()
     {
-        const bool plain = method == BICG_BICGSTAB || hat != Precond::NONE;      // the plain iteration, preconditioned or not
+        const bool plain = method == BICG_BICGSTAB || (hat != Precond::NONE && !kMethod[method].stab2);      // the plain iteration, preconditioned or not
         const bool rr = method == BICG_PIPE_BICGSTAB_RR || (method == BICG_PIPE_BICGSTAB && c->opt.rr_drift > 0.0);
         if (!c->dots.wave_mode) {
             spmv(c, v.x, v.ax, 0, nullptr, c->dots.no_dots());                       // Ax = A x0
-            if (method == BICG_BICGSTAB2) {      // the plain set-up without p, and rho1 = (r#,r0): seeded from (r0,r0), since r# = r0 here
+            if (kMethod[method].stab2) {      // the plain set-up without p, and rho1 = (r#,r0): seeded from (r0,r0), since r# = r0 here; no hat vector yet
                 launch_init_residual(v, false, false, here(), c->dots.open(1, PH_S2_INIT));
                 c->dots.close();
                 return;
@@ -534,6 +534,36 @@ struct Driver {
         launch_stab2_mr(v, here(), d.open(2, PH_S2_END)); d.close();            // V5: x, r0, u0 ; (r0,r0), (r#,r0) -> dot_r, rho1, k += 2
     }
 
+    // The sweep above on A M^-1, right-preconditioned (BICG_BICGSTAB2_DIAG / _BLOCK; include/bicgstab_hip.h): same
+    // products' outputs, dot groups and phases; the products take the hat vectors, x is updated with them, r0 stays the residual of
+    // the caller's system. The hats live in the four vectors the sweep above leaves idle:
+    //   u^0 = v.v   u^1 = v.t   r^0 = v.b   r^1 = v.ax (the set-up is done with A x0 by then)
+    // each written over all local rows before its first read in the first sweep (V1', V2', V3', V4' in this order), halo tails
+    // zeroed by run_begin and filled by the products' exchanges. Four applications of M^-1 per sweep -- u^0, r^0, u^1, r^1, in
+    // the pass that produces the vector (DIAGONAL: ten launches) or by a launch of k_bjac_apply behind it (BLOCK: fourteen), which
+    // writes the hat only: sweeps enqueued behind a stopped solve change neither x, r nor a scalar -- and two recurrences
+    // (u^0 in V3', r^0 in V4') that feed x alone.
+    void iter_stab2_hat()
+    {
+        DotGroups &d = c->dots;
+        const bool blk = hat == Precond::BLOCK;
+        const double *dinv = blk ? nullptr : c->pc.planes;
+        launch_stab2h_u0(v, dinv, here());                                      // V1': u0 = r0 - beta u0 ; u^0 = M^-1 u0
+        if (blk) precond_apply(c, v.p, v.v);
+        spmv(c, v.v, v.s, 1, v.rh, d.open(1, PH_S2_ALPHA0)); d.close();         // u1 = A u^0, (r#,u1) -> alpha
+        launch_stab2h_r0(v, dinv, here());                                      // V2': r0 -= alpha u1 ; r^0 = M^-1 r0
+        if (blk) precond_apply(c, v.r, v.b);
+        spmv(c, v.b, v.y, 1, v.rh, d.open(1, PH_S2_BETA)); d.close();           // r1 = A r^0, (r#,r1) -> rho1, beta
+        launch_stab2h_xu(v, dinv, here());                                      // V3': x += alpha u^0 (j = 0) ; u0, u^0, u1 ; u^1 = M^-1 u1
+        if (blk) precond_apply(c, v.s, v.t);
+        spmv(c, v.t, v.z, 1, v.rh, d.open(1, PH_S2_ALPHA1)); d.close();         // u2 = A u^1, (r#,u2) -> alpha
+        launch_stab2h_xrr(v, dinv, here(), d.contribute(0, false));             // V4': x, r0, r^0, r1 ; r^1 = M^-1 r1 ; (r1,r1), (r0,r1)
+        if (blk) precond_apply(c, v.y, v.ax);
+        spmv(c, v.ax, v.w, 2, v.y, d.contribute(2, false));                     // r2 = A r^1, (r1,r2), (r2,r2) -> red[2], red[3]
+        launch_stab2_dot(v, here(), d.open(5, PH_S2_MR, DOT_NOW, 4)); d.close();   // D: (r0,r2) -> red[4] ; the five -> g1, g2
+        launch_stab2h_mr(v, here(), d.open(2, PH_S2_END)); d.close();           // V5': x += g1 r^0 + g2 r^1 ; r0, u0 ; two sums -> k += 2
+    }
+
     void iter_ca()      // reference src/solver.c:217-251
     {
         launch_ca_ps(v, here());                                // p, s recurrences
@@ -604,6 +634,7 @@ struct Driver {
         case BICG_BICGSTAB: case BICG_BICGSTAB_DIAG: case BICG_BICGSTAB_BLOCK: iter_plain(); break;
         case BICG_CA_BICGSTAB: iter_ca(); break;
         case BICG_BICGSTAB2: iter_stab2(); break;
+        case BICG_BICGSTAB2_DIAG: case BICG_BICGSTAB2_BLOCK: iter_stab2_hat(); break;
         default: iter_pipe(it, force_replace, last); break;
         }
     }
@@ -664,8 +695,8 @@ void run_begin(bicg_ctx *c, int method, const bicg_options *opt_in)
     if (opt_in) o = *opt_in; else bicg_default_options(&o);
     if (method < 0 || method >= kMethods) die("bicg_run", "unknown method");
     if (diag_refused(c, method))
-        die("bicg_run", precond_kind_of(method) == Precond::DIAGONAL ? "BICG_BICGSTAB_DIAG without a preconditioner (bicg_precond_diagonal)"
-                                                                     : "BICG_BICGSTAB_BLOCK without a preconditioner (bicg_precond_block_diagonal)");
+        die("bicg_run", precond_kind_of(method) == Precond::DIAGONAL ? "a diagonally preconditioned method without its preconditioner (bicg_precond_diagonal)"
+                                                                     : "a block-Jacobi preconditioned method without its preconditioner (bicg_precond_block_diagonal)");
     if (o.max_iter < 0) o.max_iter = 0;
     if (o.check_every < 1) o.check_every = 1;
     c->method = method;
@@ -738,7 +769,7 @@ bool graph_iteration(bicg_ctx *c, Driver &d)
     // Off unless BICG_GRAPH=1: measured on one MI355X, eager in-order enqueueing already keeps the
     // GPU busy (54 us vs 60 us replayed per 17-op iteration of a 200 k-row rank); replay only pays
     // when the two-stream overlap mode is on (80 vs 105 us).
-    const bool want = c->graph_mode == 1 && m != BICG_BICGSTAB2;      // (BiCGStab(2) has no captured iteration: it runs eagerly)
+    const bool want = c->graph_mode == 1 && !kMethod[m].stab2;      // (BiCGStab(2), preconditioned or not, has no captured iteration: it runs eagerly)
     // consumer-side finish alternates between two scalar blocks: launch arguments change from one
     // iteration to the next unless the host enqueues the collectives itself
     if (c->dots.wave_mode && !hosted(c)) return false;
@@ -895,7 +926,7 @@ int run_iterate(bicg_ctx *c, int nsteps)
         const double t_chunk = now_sec();
         if (persist) persist = persist_chunk(c, chunk);   // one launch for the whole chunk (bicg_persist.hip); false: it could not be launched
         int steps = chunk;      // what the chunk advances c->it by
-        if (c->method == BICG_BICGSTAB2) {      // steps come in pairs: ceil(chunk / 2) sweeps (the device's loop condition keeps k <= max_iter)
+        if (kMethod[c->method].stab2) {      // steps come in pairs: ceil(chunk / 2) sweeps (the device's loop condition keeps k <= max_iter)
             const int sweeps = (chunk + 1) / 2;
             for (int j = 0; j < sweeps; ++j) d.iterate(c->it + 2 * j, false, j == sweeps - 1);
             steps = 2 * sweeps;

@@ -42,7 +42,7 @@ int main(int argc, char **argv)
     if (argc < 3) {
         if (me == 0) {
             printf("Usage: %s <matrix file> <method> [options]\n", argv[0]);
-            printf("Methods:\n  bicgstab\n  ca_bicgstab\n  pipe_bicgstab\n  pipe_bicgstab_rr <r> <s>\n  jacobi_bicgstab\n  block_jacobi_bicgstab [block size, 1..16; default 4]\n  bicgstab2\n");
+            printf("Methods:\n  bicgstab\n  ca_bicgstab\n  pipe_bicgstab\n  pipe_bicgstab_rr <r> <s>\n  jacobi_bicgstab\n  block_jacobi_bicgstab [block size, 1..16; default 4]\n  bicgstab2\n  jacobi_bicgstab2\n  block_jacobi_bicgstab2 [block size, 1..16; default 4]\n");
         }
 #ifdef BICG_HAVE_MPI
         MPI_Finalize();
@@ -109,6 +109,10 @@ int main(int argc, char **argv)
         k = block_jacobi_bicgstab(&diag, &offd, &info, x, r, argc >= 4 ? atoi(argv[3]) : 4);
     }
     else if (strcmp(method, "bicgstab2") == 0) k = bicgstab2(&diag, &offd, &info, x, r);               /* not in the reference */
+    else if (strcmp(method, "jacobi_bicgstab2") == 0) k = jacobi_bicgstab2(&diag, &offd, &info, x, r); /* not in the reference */
+    else if (strcmp(method, "block_jacobi_bicgstab2") == 0) {                                           /* not in the reference */
+        k = block_jacobi_bicgstab2(&diag, &offd, &info, x, r, argc >= 4 ? atoi(argv[3]) : 4);
+    }
     else if (strcmp(method, "ca_bicgstab") == 0) k = ca_bicgstab(&diag, &offd, &info, x, r);
     else if (strcmp(method, "pipe_bicgstab") == 0) k = pipe_bicgstab(&diag, &offd, &info, x, r);
     else if (strcmp(method, "pipe_bicgstab_rr") == 0) {

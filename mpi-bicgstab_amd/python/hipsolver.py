@@ -29,7 +29,9 @@ class _Methods(dict):
 
 METHODS = _Methods({"bicgstab": 0, "ca_bicgstab": 1, "pipe_bicgstab": 2, "pipe_bicgstab_rr": 3, "bicgstab_diag": 4})
 LATER_METHODS = {"bicgstab_block": 5,      # BICG_BICGSTAB_BLOCK
-                 "bicgstab2": 6}           # BICG_BICGSTAB2
+                 "bicgstab2": 6,           # BICG_BICGSTAB2
+                 "bicgstab2_diag": 7,      # BICG_BICGSTAB2_DIAG, BICG_BICGSTAB2_BLOCK: method 6 right-preconditioned with the
+                 "bicgstab2_block": 8}     # diagonal / the block diagonal the context holds
 
 _dp = C.POINTER(C.c_double)
 _up = C.POINTER(C.c_uint)
@@ -199,10 +201,11 @@ def lib():
         L.bicg_precond_apply_set_bench.restype = C.c_int
         L.bicg_csr_block_diagonal.argtypes = [C.POINTER(CSRMatrix), C.c_int, _dp]
         L.block_jacobi_bicgstab.argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp, C.c_int]
+        L.block_jacobi_bicgstab2.argtypes = L.block_jacobi_bicgstab.argtypes
         for fn in (L.bicg_precond_block_diagonal, L.bicg_precond_block_diagonal_device, L.bicg_precond_apply, L.bicg_csr_block_diagonal,
-                   L.block_jacobi_bicgstab):
+                   L.block_jacobi_bicgstab, L.block_jacobi_bicgstab2):
             fn.restype = C.c_int
-        for name in ("bicgstab", "ca_bicgstab", "pipe_bicgstab", "jacobi_bicgstab", "bicgstab2"):
+        for name in ("bicgstab", "ca_bicgstab", "pipe_bicgstab", "jacobi_bicgstab", "bicgstab2", "jacobi_bicgstab2"):
             getattr(L, name).argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp]
         L.pipe_bicgstab_rr.argtypes = [C.POINTER(CSRMatrix), C.POINTER(CSRMatrix), C.POINTER(InfoMatrix), _dp, _dp,
                                        C.c_int, C.c_int]
@@ -429,7 +432,7 @@ class Context:
         return int(lib().bicg_update_values(self.h, None if d is None or d.size == 0 else _d(d), None if o is None or o.size == 0 else _d(o)))
 
     def set_diagonal(self, d, stream=None) -> int:
-        """Install or replace the diagonal preconditioner M = diag(d) for solve("bicgstab_diag") (bicg_precond_diagonal): d as a
+        """Install or replace the diagonal preconditioner M = diag(d) for solve("bicgstab_diag" / "bicgstab2_diag") (bicg_precond_diagonal): d as a
         numpy array or a CUDA float64 torch tensor (bicg_precond_diagonal_device, ordered behind `stream`, default the current
         torch stream), in the caller's numbering; a rank without rows passes None or an empty array. Returns 0 installed, 1 refused
         (a zero or non-finite entry; what was installed stays), -1 the array is missing."""
@@ -446,7 +449,7 @@ class Context:
         return int(lib().bicg_precond_diagonal(self.h, None if d is None or d.size == 0 else _d(d)))
 
     def set_block_diagonal(self, blocks, bs: int, stream=None) -> int:
-        """Install or replace the block-Jacobi preconditioner for solve("bicgstab_block") (bicg_precond_block_diagonal): the bs x bs
+        """Install or replace the block-Jacobi preconditioner for solve("bicgstab_block" / "bicgstab2_block") (bicg_precond_block_diagonal): the bs x bs
         diagonal blocks (bs = 1..16) of this rank's rows in the caller's numbering, ceil(n / bs) * bs * bs doubles, block k's entry
         (a, j) at [(k * bs + a) * bs + j] -- what csr_block_diagonal returns --, as a numpy array or a CUDA float64 torch tensor
         (bicg_precond_block_diagonal_device, ordered behind `stream`, default the current torch stream); a rank without rows passes
@@ -860,7 +863,7 @@ def csr_block_diagonal(blocks, bs: int):
 
 
 def _installer(method: str) -> str:
-    return "set_block_diagonal" if method == "bicgstab_block" else "set_diagonal"
+    return "set_block_diagonal" if method in ("bicgstab_block", "bicgstab2_block") else "set_diagonal"
 
 
 def device_allocations() -> int:
