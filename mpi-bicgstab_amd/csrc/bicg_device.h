@@ -761,23 +761,31 @@ void launch_dot(const double *x, const double *y, uint32_t n, Scal *S, Reduce re
 unsigned vec_grid(uint32_t n);        // workgroups used by the element-wise kernels for length n
 void set_vec_grid_cap(unsigned cap);  // ranks sharing one GPU (tests): fewer workgroups per launch (0 = default)
 void preload_vec_kernels();
+
+// The preconditioner a context holds (bicg_precond.cpp; DESIGN.md sections 4.20, 4.21): at most one, of one kind. `planes` is in the
+// context's numbering, allocated through bicg_ctx::own by the first install of its kind and block size, freed by an install of the
+// other kind or another bs, by bicg_precond_clear and by bicg_destroy. NONE: planes null, bs and stride 0. (In this header for its
+// Kind, which the launch interface below takes.)
+struct Precond {
+    enum Kind { NONE = 0, DIAGONAL = 1, BLOCK = 2 };   // the values bicg_precond_kind returns
+    Kind   kind   = NONE;
+    double *planes = nullptr;   // DIAGONAL: 1 / d, one plane; BLOCK: bs planes of the inverted blocks (csrc/bicg_bjacobi.hip)
+    int    bs     = 0;          // DIAGONAL: 1
+    size_t stride = 0;          // doubles between planes. DIAGONAL: n_loc; BLOCK: n_loc rounded up to 32 (whole 256-byte lines)
+};
+
 // bicg_stab2.hip
-// the element-wise passes of a BiCGStab(2) sweep, functors on bicg_vec.h's k_vec / run_vec. Vecs as Driver::iter_stab2
-// maps them: r0 = v.r, r# = v.rh, u0 = v.p, u1 = v.s, u2 = v.z, r1 = v.y, r2 = v.w
-void launch_stab2_u0(const Vecs &v, const Launch &L);                  // V1: u0 = r0 - beta u0
-void launch_stab2_r0(const Vecs &v, const Launch &L);                  // V2: r0 -= alpha u1
-void launch_stab2_xu(const Vecs &v, const Launch &L);                  // V3: x += alpha u0 ; u0 = r0 - beta u0 ; u1 = r1 - beta u1
-void launch_stab2_xrr(const Vecs &v, const Launch &L, Reduce red);     // V4: x += alpha u0 ; r0 -= alpha u1 ; r1 -= alpha u2 ; (r1,r1), (r0,r1)
-void launch_stab2_dot(const Vecs &v, const Launch &L, Reduce red);     // D:  (r0,r2)
-void launch_stab2_mr(const Vecs &v, const Launch &L, Reduce red);      // V5: x, r0, u0 of the minimal-residual part ; (r0,r0), (r#,r0)
-// ... and of the right-preconditioned sweep (Driver::iter_stab2_hat): the same passes carrying the hat vectors
-// u^0 = v.v, u^1 = v.t, r^0 = v.b, r^1 = v.ax. dinv: the plane of 1 / d, the application dinv o v is formed in the pass that produces
-// v; null (block Jacobi): the pass leaves the application to the launch of k_bjac_apply that follows it
-void launch_stab2h_u0(const Vecs &v, const double *dinv, const Launch &L);                // V1': V1 ; u^0 = dinv o u0
-void launch_stab2h_r0(const Vecs &v, const double *dinv, const Launch &L);                // V2': V2 ; r^0 = dinv o r0
-void launch_stab2h_xu(const Vecs &v, const double *dinv, const Launch &L);                // V3': x += alpha u^0 ; u0, u1 ; u^0 = r^0 - beta u^0 ; u^1 = dinv o u1
-void launch_stab2h_xrr(const Vecs &v, const double *dinv, const Launch &L, Reduce red);   // V4': x += alpha u^0 ; r0, r1 ; r^0 -= alpha u^1 ; r^1 = dinv o r1 ; two sums
-void launch_stab2h_mr(const Vecs &v, const Launch &L, Reduce red);                        // V5': x += g1 r^0 + g2 r^1 ; r0, u0 ; two sums
+// the element-wise passes of a BiCGStab(2) sweep (DESIGN.md sections 4.23, 4.24), functors on bicg_vec.h's k_vec / run_vec. Vecs as
+// Driver::iter_stab2 maps them: r0 = v.r, r# = v.rh, u0 = v.p, u1 = v.s, u2 = v.z, r1 = v.y, r2 = v.w. `hat`: the sweep's preconditioner.
+// NONE: the passes as written here. Otherwise they carry the hat vectors u^0 = v.v, u^1 = v.t, r^0 = v.b, r^1 = v.ax as well: x is
+// updated with the hats, u^0 and r^0 follow their vectors' recurrences, and the application M^-1 v is formed in the pass that produces
+// v (DIAGONAL, from `dinv`, the plane of 1 / d, which no other kind reads) or left to the launch of k_bjac_apply that follows it (BLOCK)
+void launch_stab2_u0(const Vecs &v, Precond::Kind hat, const double *dinv, const Launch &L);                // V1: u0 = r0 - beta u0 ; u^0 = M^-1 u0
+void launch_stab2_r0(const Vecs &v, Precond::Kind hat, const double *dinv, const Launch &L);                // V2: r0 -= alpha u1 ; r^0 = M^-1 r0
+void launch_stab2_xu(const Vecs &v, Precond::Kind hat, const double *dinv, const Launch &L);                // V3: x += alpha u0 ; u0 = r0 - beta u0 ; u1 = r1 - beta u1 ; u^1 = M^-1 u1
+void launch_stab2_xrr(const Vecs &v, Precond::Kind hat, const double *dinv, const Launch &L, Reduce red);   // V4: x += alpha u0 ; r0 -= alpha u1 ; r1 -= alpha u2 ; r^1 = M^-1 r1 ; (r1,r1), (r0,r1)
+void launch_stab2_dot(const Vecs &v, const Launch &L, Reduce red);                                          // D:  (r0,r2)
+void launch_stab2_mr(const Vecs &v, Precond::Kind hat, const Launch &L, Reduce red);                        // V5: x, r0, u0 of the minimal-residual part (x with r^0, r^1) ; (r0,r0), (r#,r0)
 
 // device-side sliced-ELL plan (bicg_plan_device.hip): slice lengths + "some column is further than 32767 from its row",
 // then the column-major padded copy (32-bit columns or packed 16-bit offsets)

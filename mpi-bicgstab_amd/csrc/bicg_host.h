@@ -107,17 +107,6 @@ struct DevOwner {
     }
 };
 
-// The preconditioner a context holds (bicg_precond.cpp; DESIGN.md sections 4.20, 4.21): at most one, of one kind. `planes` is in the
-// context's numbering, allocated through bicg_ctx::own by the first install of its kind and block size, freed by an install of the
-// other kind or another bs, by bicg_precond_clear and by bicg_destroy. NONE: planes null, bs and stride 0.
-struct Precond {
-    enum Kind { NONE = 0, DIAGONAL = 1, BLOCK = 2 };   // the values bicg_precond_kind returns
-    Kind   kind   = NONE;
-    double *planes = nullptr;   // DIAGONAL: 1 / d, one plane; BLOCK: bs planes of the inverted blocks (csrc/bicg_bjacobi.hip)
-    int    bs     = 0;          // DIAGONAL: 1
-    size_t stride = 0;          // doubles between planes. DIAGONAL: n_loc; BLOCK: n_loc rounded up to 32 (whole 256-byte lines)
-};
-
 // What the host code needs to know about a solver method (the enum of include/bicgstab_hip.h), in one place
 struct MethodInfo {
     int nvec;                   // work vectors counted for the matrix-stream policy (run_begin)

@@ -512,56 +512,41 @@ struct Driver {
         if (hat == Precond::BLOCK) precond_apply(c, v.p, v.z);          // p^ = M^-1 p
     }
 
-    // One sweep of BiCGStab(2) = two BiCG steps and the two-dimensional minimal-residual step (the algorithm: include/bicgstab_hip.h at
-    // BICG_BICGSTAB2; launches, dot groups and bytes per row: DESIGN.md section 4.23). The vectors live in the slab's work vectors, all
-    // zeroed with their halo tails by run_begin, which defines u0 = u1 = u2 = 0:
-    //   r0 = v.r   r# = v.rh   u0 = v.p   u1 = v.s   u2 = v.z   r1 = v.y   r2 = v.w   (the set-up's A x0: v.ax; idle: v.v, v.t, v.b)
+    // One sweep of BiCGStab(2) = two BiCG steps and the two-dimensional minimal-residual step, as it stands or right-preconditioned
+    // (`hat`: the sweep on A M^-1; the algorithm: include/bicgstab_hip.h at BICG_BICGSTAB2 and BICG_BICGSTAB2_DIAG / _BLOCK; launches, dot
+    // groups and bytes per row: DESIGN.md sections 4.23, 4.24): one sequence of operations, dot groups and phases. The vectors live in
+    // the slab's work vectors, all zeroed with their halo tails by run_begin, which defines u0 = u1 = u2 = 0:
+    //   r0 = v.r   r# = v.rh   u0 = v.p   u1 = v.s   u2 = v.z   r1 = v.y   r2 = v.w   (the set-up's A x0: v.ax; idle without a hat: v.v, v.t, v.b)
     // rho0 / rho1 are Scal::rTr_old / rTr, g2 is Scal::omega, g1 sits in Scal::red[kRedG1]. Ten launches, five dot groups:
     // the three products with (r#, out) close a group each, the MR group's five sums come from three producers -- V4 and the product
     // r2 = A r1 contribute, the dot pass closes --, and V5 closes the sweep's last one. Always ticket groups, producer-side finish.
+    // Preconditioned, the products' outputs, dot groups and phases are the same; the products take the hat vectors, x is updated with
+    // them, r0 stays the residual of the caller's system. The hats live in the four vectors that are idle otherwise:
+    //   u^0 = v.v   u^1 = v.t   r^0 = v.b   r^1 = v.ax (the set-up is done with A x0 by then)
+    // each written over all local rows before its first read in the first sweep (V1, V2, V3, V4 in this order), halo tails zeroed by
+    // run_begin and filled by the products' exchanges. Four applications of M^-1 per sweep -- u^0, r^0, u^1, r^1, in the pass that
+    // produces the vector (DIAGONAL: ten launches) or by a launch of k_bjac_apply behind it (BLOCK: fourteen), which writes the hat
+    // only: sweeps enqueued behind a stopped solve change neither x, r nor a scalar -- and two recurrences (u^0 in V3, r^0 in V4)
+    // that feed x alone.
     void iter_stab2()
     {
         DotGroups &d = c->dots;
-        launch_stab2_u0(v, here());                                             // V1: u0 = r0 - beta u0
-        spmv(c, v.p, v.s, 1, v.rh, d.open(1, PH_S2_ALPHA0)); d.close();         // u1 = A u0, (r#,u1) -> alpha
-        launch_stab2_r0(v, here());                                             // V2: r0 -= alpha u1
-        spmv(c, v.r, v.y, 1, v.rh, d.open(1, PH_S2_BETA)); d.close();           // r1 = A r0, (r#,r1) -> rho1, beta
-        launch_stab2_xu(v, here());                                             // V3: x += alpha u0 (j = 0) ; u0 = r0 - beta u0 ; u1 = r1 - beta u1
-        spmv(c, v.s, v.z, 1, v.rh, d.open(1, PH_S2_ALPHA1)); d.close();         // u2 = A u1, (r#,u2) -> alpha
-        launch_stab2_xrr(v, here(), d.contribute(0, false));                    // V4: x, r0, r1 ; (r1,r1), (r0,r1) -> red[0], red[1]
-        spmv(c, v.y, v.w, 2, v.y, d.contribute(2, false));                      // r2 = A r1, (r1,r2), (r2,r2) -> red[2], red[3]
-        launch_stab2_dot(v, here(), d.open(5, PH_S2_MR, DOT_NOW, 4)); d.close();   // D: (r0,r2) -> red[4] ; the five -> g1, g2
-        launch_stab2_mr(v, here(), d.open(2, PH_S2_END)); d.close();            // V5: x, r0, u0 ; (r0,r0), (r#,r0) -> dot_r, rho1, k += 2
-    }
-
-    // The sweep above on A M^-1, right-preconditioned (BICG_BICGSTAB2_DIAG / _BLOCK; include/bicgstab_hip.h): same
-    // products' outputs, dot groups and phases; the products take the hat vectors, x is updated with them, r0 stays the residual of
-    // the caller's system. The hats live in the four vectors the sweep above leaves idle:
-    //   u^0 = v.v   u^1 = v.t   r^0 = v.b   r^1 = v.ax (the set-up is done with A x0 by then)
-    // each written over all local rows before its first read in the first sweep (V1', V2', V3', V4' in this order), halo tails
-    // zeroed by run_begin and filled by the products' exchanges. Four applications of M^-1 per sweep -- u^0, r^0, u^1, r^1, in
-    // the pass that produces the vector (DIAGONAL: ten launches) or by a launch of k_bjac_apply behind it (BLOCK: fourteen), which
-    // writes the hat only: sweeps enqueued behind a stopped solve change neither x, r nor a scalar -- and two recurrences
-    // (u^0 in V3', r^0 in V4') that feed x alone.
-    void iter_stab2_hat()
-    {
-        DotGroups &d = c->dots;
         const bool blk = hat == Precond::BLOCK;
-        const double *dinv = blk ? nullptr : c->pc.planes;
-        launch_stab2h_u0(v, dinv, here());                                      // V1': u0 = r0 - beta u0 ; u^0 = M^-1 u0
+        const double *dinv = hat == Precond::DIAGONAL ? c->pc.planes : nullptr;
+        launch_stab2_u0(v, hat, dinv, here());                                  // V1: u0 = r0 - beta u0 ; u^0 = M^-1 u0
         if (blk) precond_apply(c, v.p, v.v);
-        spmv(c, v.v, v.s, 1, v.rh, d.open(1, PH_S2_ALPHA0)); d.close();         // u1 = A u^0, (r#,u1) -> alpha
-        launch_stab2h_r0(v, dinv, here());                                      // V2': r0 -= alpha u1 ; r^0 = M^-1 r0
+        spmv(c, hat ? v.v : v.p, v.s, 1, v.rh, d.open(1, PH_S2_ALPHA0)); d.close();   // u1 = A u0 (A u^0), (r#,u1) -> alpha
+        launch_stab2_r0(v, hat, dinv, here());                                  // V2: r0 -= alpha u1 ; r^0 = M^-1 r0
         if (blk) precond_apply(c, v.r, v.b);
-        spmv(c, v.b, v.y, 1, v.rh, d.open(1, PH_S2_BETA)); d.close();           // r1 = A r^0, (r#,r1) -> rho1, beta
-        launch_stab2h_xu(v, dinv, here());                                      // V3': x += alpha u^0 (j = 0) ; u0, u^0, u1 ; u^1 = M^-1 u1
+        spmv(c, hat ? v.b : v.r, v.y, 1, v.rh, d.open(1, PH_S2_BETA)); d.close();     // r1 = A r0 (A r^0), (r#,r1) -> rho1, beta
+        launch_stab2_xu(v, hat, dinv, here());                                  // V3: x += alpha u0 (u^0; j = 0) ; u0, u^0, u1 ; u^1 = M^-1 u1
         if (blk) precond_apply(c, v.s, v.t);
-        spmv(c, v.t, v.z, 1, v.rh, d.open(1, PH_S2_ALPHA1)); d.close();         // u2 = A u^1, (r#,u2) -> alpha
-        launch_stab2h_xrr(v, dinv, here(), d.contribute(0, false));             // V4': x, r0, r^0, r1 ; r^1 = M^-1 r1 ; (r1,r1), (r0,r1)
+        spmv(c, hat ? v.t : v.s, v.z, 1, v.rh, d.open(1, PH_S2_ALPHA1)); d.close();   // u2 = A u1 (A u^1), (r#,u2) -> alpha
+        launch_stab2_xrr(v, hat, dinv, here(), d.contribute(0, false));         // V4: x, r0, r^0, r1 ; r^1 = M^-1 r1 ; (r1,r1), (r0,r1) -> red[0], red[1]
         if (blk) precond_apply(c, v.y, v.ax);
-        spmv(c, v.ax, v.w, 2, v.y, d.contribute(2, false));                     // r2 = A r^1, (r1,r2), (r2,r2) -> red[2], red[3]
+        spmv(c, hat ? v.ax : v.y, v.w, 2, v.y, d.contribute(2, false));         // r2 = A r1 (A r^1), (r1,r2), (r2,r2) -> red[2], red[3]
         launch_stab2_dot(v, here(), d.open(5, PH_S2_MR, DOT_NOW, 4)); d.close();   // D: (r0,r2) -> red[4] ; the five -> g1, g2
-        launch_stab2h_mr(v, here(), d.open(2, PH_S2_END)); d.close();           // V5': x += g1 r^0 + g2 r^1 ; r0, u0 ; two sums -> k += 2
+        launch_stab2_mr(v, hat, here(), d.open(2, PH_S2_END)); d.close();       // V5: x (with r^0, r^1), r0, u0 ; (r0,r0), (r#,r0) -> dot_r, rho1, k += 2
     }
 
     void iter_ca()      // reference src/solver.c:217-251
@@ -633,8 +618,7 @@ struct Driver {
         switch (method) {
         case BICG_BICGSTAB: case BICG_BICGSTAB_DIAG: case BICG_BICGSTAB_BLOCK: iter_plain(); break;
         case BICG_CA_BICGSTAB: iter_ca(); break;
-        case BICG_BICGSTAB2: iter_stab2(); break;
-        case BICG_BICGSTAB2_DIAG: case BICG_BICGSTAB2_BLOCK: iter_stab2_hat(); break;
+        case BICG_BICGSTAB2: case BICG_BICGSTAB2_DIAG: case BICG_BICGSTAB2_BLOCK: iter_stab2(); break;
         default: iter_pipe(it, force_replace, last); break;
         }
     }

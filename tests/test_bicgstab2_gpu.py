@@ -1,5 +1,5 @@
-"""`-m gpu`, one rank: BiCGStab(2), method BICG_BICGSTAB2 = 6 (Driver::iter_stab2 in csrc/bicg_solver.cpp, the PH_S2_* phases of
-csrc/bicg_devfn.h, the functors of csrc/bicg_stab2.hip) through Context.solve("bicgstab2") and the run_* calls.
+"""`-m gpu`, one rank: BiCGStab(2), method BICG_BICGSTAB2 = 6 (Driver::iter_stab2 without a hat in csrc/bicg_solver.cpp, the PH_S2_* phases of
+csrc/bicg_devfn.h, the functors of csrc/bicg_stab2.hip in their form for Precond::NONE) through Context.solve("bicgstab2") and the run_* calls.
 
 Contexts are created under switches(persist=0), matrices, x0 and b are those of tests/test_precond_gpu.py (its Bundle), the
 reference is the numpy restatement tests/bicgstab2_ref.py.

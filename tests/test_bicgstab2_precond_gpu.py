@@ -1,5 +1,6 @@
 """`-m gpu`, one rank: the right-preconditioned BiCGStab(2), methods BICG_BICGSTAB2_DIAG = 7 and BICG_BICGSTAB2_BLOCK = 8
-(Driver::iter_stab2_hat in csrc/bicg_solver.cpp, the FS2H* functors of csrc/bicg_stab2.hip) through
+(Driver::iter_stab2 with a hat in csrc/bicg_solver.cpp, the DIAGONAL / BLOCK forms of the FS2* functors of csrc/bicg_stab2.hip, which
+method 6 shares with them as their NONE form) through
 Context.solve("bicgstab2_diag" / "bicgstab2_block") and the run_* calls.
 
 Contexts are created under switches(persist=0); matrices, x0, b and the powers of two d are those of tests/test_precond_gpu.py (its
