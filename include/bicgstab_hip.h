@@ -714,6 +714,9 @@ int bicg_last_shifted_persistent(bicg_ctx *ctx);
  * runs take it), 0 the row-major kernel k_spmm_sell (BICG_PLAN="spmm-window=0", and layouts without clusters or window runs).
  * In all three the vectors' columns are bit-identical to bicg_spmv of each vector. */
 int bicg_last_spmm_windowed(bicg_ctx *ctx);
+/* Rows per tile of that pass when it ran k_spmm_pipe: 512, or 256 (the window does not fit 512-row tiles, or
+ * BICG_TEST="spmm-tile=256"); 0 after any other kernel (k_spmm_jpipe, k_spmm_win, k_spmm_sell). Read-only. */
+int bicg_last_spmm_tile(bicg_ctx *ctx);
 unsigned long long bicg_spmv_matrix_bytes(bicg_ctx *ctx);
 
 /* ---------------------------------------------------------------------------------------------

@@ -437,6 +437,7 @@ unsigned int bicg_product_kernels(int reset)
 unsigned long long bicg_spmv_matrix_bytes(bicg_ctx *c) { return stencil_product(c) ? c->stencil_matrix_bytes : c->matrix_bytes; }
 int bicg_last_shifted_persistent(bicg_ctx *c) { return c->last_shifted_persist ? 1 : 0; }
 int bicg_last_spmm_windowed(bicg_ctx *c) { return c->mm_win ? (c->mm_dma ? 2 : 1) : 0; }      // 2: the pipelined kernel (bicg_spmm.hip)
+int bicg_last_spmm_tile(bicg_ctx *c) { return c->mm_win && c->mm_dma ? c->mm_tile : 0; }
 
 unsigned int bicg_ctx_flags(bicg_ctx *c)
 {

@@ -595,7 +595,8 @@ void preload_spmm_sell_kernels();
 // bicg_spmm.hip, bicg_spmm_jag.hip
 // pipelined form (bicg_spmm.hip, k_spmm_pipe): the window of the next step copied global -> LDS by the DMA path while the current one
 // multiplies, persistent workgroups over consecutive groups; padded 16-bit layouts with clusters (hipErrorInvalidValue: not this block)
-hipError_t launch_spmm_pipe(const SpmmArgs &a, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// tile_out (optional): the rows per tile of the launch, 512 or 256 (untouched when the block does not qualify)
+hipError_t launch_spmm_pipe(const SpmmArgs &a, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, int *tile_out = nullptr);
 // the same pipeline on jagged slices with x windows (bicg_spmm_jag.hip, k_spmm_jpipe); hipErrorInvalidValue: the block does not qualify
 hipError_t launch_spmm_jpipe(const SpmmArgs &a, bool with_offd, hipStream_t st, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 void preload_spmm_kernels();

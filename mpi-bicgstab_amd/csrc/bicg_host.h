@@ -356,6 +356,7 @@ struct bicg_ctx {
     bool mm_win = false;         // the last SpMM pass ran the windowed kernel (vectors stay shift-major, X staged in LDS)
     int  mm_win_env = 3;         // BICG_PLAN="spmm-window=0": the row-major kernel, 1: k_spmm_win everywhere, 3 (default): k_spmm_pipe where the block qualifies
     bool mm_dma = false;         // the last SpMM pass ran the pipelined kernel (bicg_spmm.hip)
+    int  mm_tile = 0;            // ... k_spmm_pipe with this many rows per tile (512 or 256); 0: any other kernel
 
     // multi-RHS BiCGStab (bicg_solve_multi, bicg_multi.cpp): one set of kSpmmCols columns of X, R, R#, P, S, Y in one slab, the
     // set's scalar block, its dot partials and its trace; allocated by the first call. The traces of the last call's sets are

@@ -330,13 +330,15 @@ void spmm_pass(bicg_ctx *c, int nvec, const double *sigma_host, bool with_b, boo
         a.sigma = c->mm_sigma;
     }
     c->mm_dma = false;
+    c->mm_tile = 0;
     if (c->mm_win) {
         a.xs = in; a.ys = with_b ? nullptr : out; a.vstride = st; a.nvec = nvec; a.wslots = wslots;
         a.tail_most = c->jag_tail16_max;
         if (const char *sv = test_tok("spmm-skip")) a.dbg = atoi(sv);
         if (!c->sell.win_slots) a.cl = c->fw;
         // the pipelined form where the block qualifies (BICG_PLAN="spmm-window=1": k_spmm_win everywhere)
-        c->mm_dma = c->mm_win_env == 3 && !a.dbg && launch_spmm_pipe(a, !c->single(), c->sc, e0, e1) == hipSuccess;
+        c->mm_dma = c->mm_win_env == 3 && !a.dbg && launch_spmm_pipe(a, !c->single(), c->sc, e0, e1, &c->mm_tile) == hipSuccess;
+        if (!c->mm_dma) c->mm_tile = 0;
         // ... and its form for ragged rows (jagged slices with x windows: bicg_spmm_jag.hip)
         if (!c->mm_dma && c->mm_win_env == 3 && c->sell.win_slots && c->win_near16) c->mm_dma = launch_spmm_jpipe(a, !c->single(), c->sc, e0, e1) == hipSuccess;
         if (!c->mm_dma && launch_spmm_win(a, !c->single(), c->sc, e0, e1) != hipSuccess) die("bicg_spmm", "the windowed kernel could not be launched (BICG_PLAN=spmm-window=0 selects the row-major form)");

@@ -409,7 +409,7 @@ static void spmm_pipe_shape(const SpmmArgs &a, unsigned ntiles, unsigned residen
     }
 }
 
-hipError_t launch_spmm_pipe(const SpmmArgs &a0, bool with_offd, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+hipError_t launch_spmm_pipe(const SpmmArgs &a0, bool with_offd, hipStream_t st, hipEvent_t e0, hipEvent_t e1, int *tile_out)
 {
     if (a0.ngroups == 0) return hipSuccess;
     SpmmArgs a = a0;
@@ -423,6 +423,7 @@ hipError_t launch_spmm_pipe(const SpmmArgs &a0, bool with_offd, hipStream_t st, 
     if (tile == 512 && !spmm_pipe_plan(a0, 512, f, W)) tile = 256;
     if (tile == 256 && !spmm_pipe_plan(a0, 256, f, W)) return hipErrorInvalidValue;
     a.cl = f; a.wslots = W;
+    if (tile_out) *tile_out = tile;
     const unsigned ntiles = (a0.nrows + (unsigned)tile - 1u) / (unsigned)tile, ngroups_all = a0.ngroups;
     a.ngroups = ntiles;                                                         // the kernel counts tiles
     unsigned grid = 0;

@@ -73,7 +73,7 @@ EXPORTS = [
     "bicg_comm_unique_id", "bicg_comm_init_rccl", "bicg_comm_init_host", "bicg_comm_init_mpi",
     "bicg_comm_init_single", "bicg_comm_finalize", "bicg_comm_selftest_rccl", "bicg_comm_rccl_loadable", "bicg_comm_last_error", "bicg_section_times", "bicg_comm_rank", "bicg_comm_size",
     "bicg_default_options", "bicg_create", "bicg_destroy", "bicg_solve", "bicg_load", "bicg_run", "bicg_fetch",
-    "bicg_run_begin", "bicg_run_iterate", "bicg_run_iterate_timed", "bicg_run_end", "bicg_sync", "bicg_trace", "bicg_spmv", "bicg_dot", "bicg_spmv_bench", "bicg_plan_info", "bicg_ctx_flags", "bicg_spmm", "bicg_device_matrix_bytes", "bicg_uniform_entries", "bicg_constant_entries", "bicg_masked_rows", "bicg_stencil_info", "bicg_stencil_rows_per_lane", "bicg_comm_wait_stats", "bicg_plan_collisions", "bicg_product_kernels", "bicg_spmv_matrix_bytes", "bicg_last_shifted_persistent", "bicg_last_spmm_windowed", "bicg_dropin_context", "bicg_dropin_release", "bicg_dropin_stats",
+    "bicg_run_begin", "bicg_run_iterate", "bicg_run_iterate_timed", "bicg_run_end", "bicg_sync", "bicg_trace", "bicg_spmv", "bicg_dot", "bicg_spmv_bench", "bicg_plan_info", "bicg_ctx_flags", "bicg_spmm", "bicg_device_matrix_bytes", "bicg_uniform_entries", "bicg_constant_entries", "bicg_masked_rows", "bicg_stencil_info", "bicg_stencil_rows_per_lane", "bicg_comm_wait_stats", "bicg_plan_collisions", "bicg_product_kernels", "bicg_spmv_matrix_bytes", "bicg_last_shifted_persistent", "bicg_last_spmm_windowed", "bicg_last_spmm_tile", "bicg_dropin_context", "bicg_dropin_release", "bicg_dropin_stats",
     "bicg_mtx_load_block", "bicg_mtx_free", "bicg_partition", "bicg_halo_plan", "bicg_halo_send_counts", "bicg_halo_send_lists", "bicg_row_blocks", "bicg_window_plan", "bicg_window_slot", "bicg_version", "bicg_has_experiments", "bicg_switch_value", "bicg_switch_unknown", "bicg_stream_bench", "bicg_create_device_csr", "bicg_stencil7_device", "bicg_device_free", "bicg_persist_plan", "bicg_set_plan_threads", "bicg_sell_plan_digest", "bicg_spmv_launch_plan", "bicg_dot_group_plan",
     "bicg_reorder_plan", "bicg_permute_block", "bicg_reorder_info",
     "bicg_solve_multi", "bicg_multi_trace", "bicg_comm_counts", "bicg_device_allocations",
@@ -142,6 +142,7 @@ def lib():
         L.bicg_product_kernels.argtypes = [C.c_int]; L.bicg_product_kernels.restype = C.c_uint
         L.bicg_last_shifted_persistent.argtypes = [C.c_void_p]
         L.bicg_last_spmm_windowed.argtypes = [C.c_void_p]
+        L.bicg_last_spmm_tile.argtypes = [C.c_void_p]
         L.bicg_shifted_residuals.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int, _dp]
         L.bicg_default_options.argtypes = [C.POINTER(Options)]
         L.bicg_comm_unique_id.argtypes = [C.c_void_p]
@@ -219,7 +220,8 @@ SWITCHES = {k: ("BICG_PLAN", k.replace("_", "-")) for k in (
     "spmm", "spmm_window", "fuse_pipe", "pipe_probe", "halo_fused", "window_list", "wide", "reorder", "handover", "halo_set")}
 SWITCHES.update(persist=("BICG_PERSIST", "0"), persist_chunk=("BICG_PERSIST", "chunk"), persist_shifted=("BICG_PERSIST", "shifted"),
                 force_comm=("BICG_TEST", "force-comm"), spin_ticks=("BICG_TEST", "spin-ticks"),
-                p2p_fault_after=("BICG_TEST", "p2p-fault-after"), plan_collide=("BICG_TEST", "plan-collide"))
+                p2p_fault_after=("BICG_TEST", "p2p-fault-after"), plan_collide=("BICG_TEST", "plan-collide"),
+                spmm_tile=("BICG_TEST", "spmm-tile"), spmm_gstep=("BICG_TEST", "spmm-gstep"))
 SWITCH_VARS = ("BICG_PLAN", "BICG_PERSIST", "BICG_TEST")
 
 
@@ -823,6 +825,10 @@ class Context:
     def last_spmm_kind(self) -> str:
         """which SpMM kernel the last pass ran: "pipelined" (k_spmm_pipe), "windowed" (k_spmm_win) or "rowmajor" (k_spmm_sell)"""
         return ("rowmajor", "windowed", "pipelined")[int(lib().bicg_last_spmm_windowed(self.h))]
+
+    def last_spmm_tile(self) -> int:
+        """rows per tile of the last pass when it ran k_spmm_pipe (512 or 256); 0 after any other kernel"""
+        return int(lib().bicg_last_spmm_tile(self.h))
 
     def last_shifted_persistent(self) -> bool:
         return bool(lib().bicg_last_shifted_persistent(self.h))

@@ -1,6 +1,6 @@
 """Byte comparisons and the integer systems behind them -- a plain helper of the tests that put a product kernel on its plan limits
 (tests/test_ragged_limits_gpu.py on tests/ragged_cases.py, tests/test_csr_limits_gpu.py and tests/mp_csr_workers.py on
-tests/csr_cases.py). Nothing in here touches a GPU; the library appears only through the context a caller hands to `check_first_dots`."""
+tests/csr_cases.py, tests/test_padded_limits_gpu.py and tests/mp_padded_workers.py on tests/padded_cases.py). Nothing in here touches a GPU; the library appears only through the context a caller hands to `check_first_dots`."""
 from __future__ import annotations
 
 from fractions import Fraction
